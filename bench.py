@@ -2,7 +2,8 @@
 """bench.py -- the DINT server hot path on MI355X, one step = one batch of synthetic wire messages
 already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload tatp|smallbank|store|fasst] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload tatp|smallbank|store|fasst] [--full]
+                    [--dump-outputs DIR] ...
 
 Default workload (BASELINE.json metric "Mtxn/s ... TATP Zipf-0.8", configs[3]): the TATP transaction
 mix against 1M subscribers.  W virtual clients run the reference client's seven transactions in lock
@@ -11,6 +12,9 @@ request batches (one per replicated shard server, as in the reference's 3-server
 three engines of the GPU process.  The closed loop is first run once and recorded; the timed region
 replays the recorded batches from HBM (no host work, no PCIe) and the replies are checked byte for byte
 against the recorded run -- and, in the cpu_baseline leg, against the CPU oracle on the same stream.
+A plain run does only that: set up, warm up, time the K steps, print the line (`--dump-outputs DIR`: and write the
+replies of the last step).  `--full` adds every other leg -- CPU baseline and reference, the other workloads, the
+exchange leg, the GPU-resident closed loop, the PCIe path, repeats, latency, kernel times and rooflines.
 Other workloads: `smallbank` (BASELINE configs[4], same machinery), `store` (configs[2]: 16.8M keys, 95/5
 read/write), `fasst` (configs[1]: lock_fasst, 64k batches; `--slots 36000000` = the reference's table).
 
@@ -40,6 +44,9 @@ sys.path.insert(0, ROOT)
 BATCH = 65536
 KV_PASS = 1 << 20  # requests per kernel pass of the store / tatp / smallbank engines (dint_config.max_pass = 0)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+# tatp / smallbank: steps of the recorded trace (~2 GB of HBM per step of 16 epochs); more timed steps replay it in laps
+MAX_WARM_STEPS, MAX_TIMED_STEPS = 5, 20
+DUMP_SAMPLE = 1 << 16  # reply messages of the last step written by --dump-outputs (a fixed, seeded sample)
 
 
 def parse():
@@ -79,7 +86,7 @@ def parse():
     ap.add_argument("--no-as-shipped", action="store_true", help="skip the as-shipped tatp/udp deployment leg (three reference "
                     "server processes, ~27 GB of host memory)")
     ap.add_argument("--legs", default="all", choices=["all", "gpu", "headline"],
-                    help="one switch over the --no-* flags: all = every leg (the driver's run); gpu = no CPU leg (cpu baseline, "
+                    help="with --full, one switch over the --no-* flags: all = every leg; gpu = no CPU leg (cpu baseline, "
                          "reference, as-shipped servers, UDP shim); headline = the timed region, its kernel times and roofline "
                          "only (what tools/profile_bench.py runs under rocprofv3)")
     ap.add_argument("--replay", default="inplace", choices=["inplace", "copy"],
@@ -90,7 +97,16 @@ def parse():
                     help="tatp / store replay: plain dint_submit_device calls (r05), no dint_submit_device_ahead")
     ap.add_argument("--sweep-clients", action="store_true",
                     help="tatp / smallbank: abort rate and Mtxn/s at 4096 / 32768 / 131072 / 524288 closed-loop clients")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline (CPU baseline and reference, other workloads, the exchange leg, closed "
+                         "loop, PCIe path, repeats, latency, kernel times and rooflines; --legs / --no-* pick among them).  "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path answered in its last step to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    args.lean = not args.full
+    if args.lean:  # the headline alone: none of the side legs, nothing that takes runs of its own
+        args.legs = "headline"
     if args.legs in ("gpu", "headline"):
         args.no_cpu_baseline = args.no_cpu_reference = args.no_shim = args.no_as_shipped = True
     args.no_pass_1m = args.no_inputs_ready = False
@@ -262,7 +278,7 @@ def rand_roofline(extra, ops_per_s, dev, U, u_what, table_gb):
 
 
 def pct(a, q):
-    return round(float(np.percentile(a, q)), 2)
+    return round(float(np.percentile(a, q)), 2) if len(a) else None  # (None: not measured, a plain run)
 
 
 # ----------------------------------------------------------------------------- lock_fasst / lock_2pl / log
@@ -472,6 +488,9 @@ def bench_lock(args, world, rank, dev, transport, kind):
     barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world, transport)
     got = d_rep.cpu().numpy().tobytes()
+    if args.dump_outputs and rank == 0:
+        g = np.frombuffer(got, np.uint8)
+        dump_messages(args.dump_outputs, [(b - (n_batches - B), 0, g[b * BATCH * msg:(b + 1) * BATCH * msg]) for b in range(n_batches - B, n_batches)], msg)
     # every reply byte of the recorded closed loop (one GPU: the replay applies the same requests in the same order;
     # several: a 64k batch takes 16 epochs of rank 0 before rank 1's, the recording interleaved them epoch by epoch)
     replay_ok = (got == recorded.tobytes()) if world == 1 else None
@@ -658,6 +677,9 @@ def bench_log(args, world, rank, dev, transport):
     barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world, transport)
     got = d_rep.cpu().numpy().tobytes()
+    if args.dump_outputs and rank == 0:
+        g = np.frombuffer(got, np.uint8)
+        dump_messages(args.dump_outputs, [(b - (n_batches - B), 0, g[b * BATCH * msg:(b + 1) * BATCH * msg]) for b in range(n_batches - B, n_batches)], msg)
     lat = []
     for b in range(W * B, min(n_batches, W * B + 100)):
         sync()
@@ -809,6 +831,8 @@ def bench_store(args, world, rank, dev, transport):
     barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world, transport)
     got = d_rep.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_messages(args.dump_outputs, [(b - (n_batches - B), 0, got[b * NB * msg:(b + 1) * NB * msg]) for b in range(n_batches - B, n_batches)], msg)
     reset()
     lat = []
     for b in range(W * B, min(n_batches, W * B + 100)):
@@ -1115,6 +1139,119 @@ def txn_U(kind, rp, lo, hi):
     return units / max(1, tot)
 
 
+_HIP = None
+
+
+def _hip():
+    """the HIP runtime this process runs on (torch's copy, which libdint.so shares: dint_amd/_lib.py): device copies
+    between raw device pointers"""
+    global _HIP
+    if _HIP is None:
+        import ctypes as C
+
+        import torch  # noqa: F401
+        path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
+        L = C.CDLL(path)  # the mapped copy: the same handle, not a second runtime
+        L.hipMemcpy.restype, L.hipMemcpy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _HIP = L
+    return _HIP
+
+
+def record_on_gpu(grp, wl, C, n_rows, first_client, zipf, n_epochs, inplace, ahead):
+    """`Replay.recording` with the clients on the GPU: dint_amd.driver.GpuDriver emits the request stream of the host
+    Driver bit for bit (tests/test_gpu_gdriver.py), so the trace is the same, recorded in a fraction of a second instead
+    of the host clients' ~0.1 s per epoch.  An epoch: emit -> the three engines answer the batches in place
+    (dint_submit_segments_multi, as GpuLoop) -> consume; requests and replies are copied on the device into the Replay's
+    buffers.  Returns (replay, finished txns per epoch, client stats), or None if a batch overflowed the clients' buffers."""
+    import ctypes as C_
+
+    import torch
+
+    from dint_amd.driver import N_SHARDS, GpuDriver
+    from dint_amd.engine import submit_segments_multi
+    from dint_amd.replay import Replay
+
+    hip, msg = _hip(), grp.msg
+    cap = min(e.pass_max for e in grp.engines)
+    gd = GpuDriver(wl, C, n_rows, cap, first_client=first_client, zipf_theta=zipf)
+    rp, done, last = Replay(msg_size=msg, inplace=inplace, ahead=ahead), [], 0
+    st = torch.cuda.Stream()
+    cnt = (C_.c_uint32 * N_SHARDS)()
+
+    def copy(n):  # the current epoch's batches (device -> device)
+        out = []
+        for s in range(N_SHARDS):
+            t = torch.empty(n[s] * msg, dtype=torch.uint8, device="cuda")
+            if n[s] and hip.hipMemcpy(t.data_ptr(), gd.batch_ptr[s], n[s] * msg, 3):  # hipMemcpyDeviceToDevice
+                raise RuntimeError("hipMemcpy (device to device) failed")
+            out.append(t)
+        return out
+
+    for _ in range(n_epochs):
+        gd.next(st.cuda_stream)
+        st.synchronize()
+        if hip.hipMemcpy(C_.addressof(cnt), gd.counts_ptr, C_.sizeof(cnt), 2):  # hipMemcpyDeviceToHost
+            raise RuntimeError("hipMemcpy (device to host) failed")
+        n = list(cnt)
+        if max(n) > cap:
+            break
+        req = copy(n)
+        submit_segments_multi(grp.engines, gd.batch_ptr, 1, [cap] * N_SHARDS, cap * msg,
+                              [gd.counts_ptr + 4 * s for s in range(N_SHARDS)], 0, st.cuda_stream)
+        grp.sync()
+        rep = copy(n)
+        gd.consume(0)  # in a kernel of its own at once (not fused into the next emit): the stats count this epoch's replies
+        now = gd.stats()["txns"]
+        done.append(now - last)
+        last = now
+        rp.counts.append(n)
+        rp.d_req.append(req)
+        rp.d_want.append(rep)
+        rp.d_rep.append([torch.empty(n[s] * msg, dtype=torch.uint8, device="cuda") for s in range(N_SHARDS)])
+    stats = gd.stats()
+    gd.close()
+    torch.cuda.synchronize()
+    if stats["overflow"] or len(done) < n_epochs:
+        return None
+    return rp, done, stats
+
+
+def dump_replies(out_dir, rp, lo, hi):
+    """--dump-outputs for tatp / smallbank: the replies of epochs [lo, hi) (the last timed step), per epoch and shard server"""
+    from dint_amd.driver import N_SHARDS
+
+    dump_messages(out_dir, [(e - lo, s, rp.d_rep[e][s]) for e in range(lo, hi) for s in range(N_SHARDS)], rp.msg)
+
+
+def dump_messages(out_dir, parts, msg):
+    """--dump-outputs: what the timed path answered in its last step, `parts` = [(batch, shard, reply bytes)] (uint8 tensors or
+    arrays), as float arrays --
+    replies.npy: DUMP_SAMPLE reply messages drawn with a fixed seed, one byte per column (float32);
+    reply_index.npy: their (batch in the step, shard, message) (float64);
+    reply_sums.npy: per part its batch, shard, message count, byte sum and position-weighted byte sum over ALL its replies
+    (float64, exact)."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    parts = [(b, s, torch.from_numpy(np.array(r)) if isinstance(r, np.ndarray) else r) for b, s, r in parts]
+    sums = []
+    for b, s, r in parts:
+        v = r.long()
+        w = torch.arange(v.numel(), device=v.device, dtype=torch.int64) % 251 + 1
+        sums.append((b, s, r.numel() // msg, float(v.sum()), float((v * w).sum())))
+    starts = np.cumsum([0] + [x[2] for x in sums])
+    pick = np.sort(np.random.default_rng(0xD1A7).choice(starts[-1], min(DUMP_SAMPLE, int(starts[-1])), replace=False))
+    rows, index = [np.zeros((0, msg), np.float32)], [np.zeros((0, 3))]
+    for k, (b, s, r) in enumerate(parts):
+        sel = pick[(pick >= starts[k]) & (pick < starts[k + 1])] - starts[k]
+        if len(sel):
+            rows.append(r.view(-1, msg)[torch.from_numpy(sel).to(r.device)].cpu().numpy().astype(np.float32))
+            index.append(np.stack([np.full(len(sel), b), np.full(len(sel), s), sel], axis=1).astype(np.float64))
+    np.save(os.path.join(out_dir, "replies.npy"), np.concatenate(rows))
+    np.save(os.path.join(out_dir, "reply_index.npy"), np.concatenate(index))
+    np.save(os.path.join(out_dir, "reply_sums.npy"), np.array(sums, np.float64).reshape(-1, 5))
+
+
 def bench_txn(args, world, rank, dev, transport, kind):
     import torch
 
@@ -1135,25 +1272,35 @@ def bench_txn(args, world, rank, dev, transport, kind):
         n_rows = args.accounts if args.accounts else 10_000_000 * world
         alg_tab, log_types, dtype = SB_ALG, SB_LOG_TYPES, "u64"
     zipf = theta if theta > 0 else None
-    E0, E1 = W * B, (W + K) * B  # timed epochs
+    # The recorded trace: the warm-up epochs and the timed epochs, each capped (every recorded epoch stays in HBM).  Epochs
+    # [0, E0) are the warm-up, [E0, E1) the timed stretch; a longer run replays the timed stretch in laps (run_laps below).
+    E0, E1 = min(W, MAX_WARM_STEPS) * B, (min(W, MAX_WARM_STEPS) + min(K, MAX_TIMED_STEPS)) * B
     t_setup = time.perf_counter()
     grp = ShardGroup(wl, n_rows, device=dev, rank=rank, world=world, transport=None if world > 1 else "self",
                      force_exchange=args.force_exchange, n_max=KV_PASS, flags=int(os.environ.get("DINT_BENCH_FLAGS", "0")))
     grp.sync()
     grp.snapshot()
-    drv = Driver(wl, C, n_rows, first_client=rank * C, zipf_theta=zipf)
     # the closed loop, once, through the real engines; every epoch stays in HBM.  The replay answers in place and announces
     # every next batch (r06; --replay copy --no-ahead = r05's replay); through the exchange the batches are routed copies anyway
     inplace = args.replay == "inplace" and grp.router is None
-    rp, done, _ = Replay.recording(drv, grp, E1, inplace=inplace, ahead=not args.no_ahead and grp.router is None)
-    stats = drv.stats()
+    rec = None
+    if grp.router is None and getattr(args, "lean", False):  # (--full: the host clients, whose run the closed-loop leg is held to)
+        rec = record_on_gpu(grp, wl, C, n_rows, rank * C, zipf, E1, inplace, not args.no_ahead)
+        if rec is None:  # a batch overflowed the device clients' buffers: the host clients record the same trace
+            grp.restore()
+    if rec is not None:
+        rp, done, stats = rec
+    else:
+        drv = Driver(wl, C, n_rows, first_client=rank * C, zipf_theta=zipf)
+        rp, done, _ = Replay.recording(drv, grp, E1, inplace=inplace, ahead=not args.no_ahead and grp.router is None)
+        stats = drv.stats()
     grp.sync()
     caps = grp.router.tighten_caps() if grp.router is not None else None  # slot capacities from the recorded maxima
     grp.restore()
     torch.cuda.synchronize()
     t_setup = time.perf_counter() - t_setup
 
-    # The recording above is host-bound (seconds of a mostly idle GPU): the first GPU-bound stretch after it runs at idle clocks
+    # The recording above leaves the GPU mostly idle (host clients, or one synchronised epoch at a time): the first GPU-bound stretch after it runs at idle clocks
     # for tens of milliseconds (r05: the W warm-up steps alone -- 7 ms -- left the timed region 3x slower than its repeats).
     # Untimed spin-up first: the warm-up epochs replayed until the GPU has been busy for ~0.3 s; then the state of the
     # recording's start again, the W warm-up steps, the K timed steps.
@@ -1164,20 +1311,39 @@ def bench_txn(args, world, rank, dev, transport, kind):
         grp.sync()
         grp.restore()
     grp.sync()
-    rp.reset()  # (in-place replay: the receive buffers hold the pristine requests again -- before the clock starts)
-    rp.run(grp, 0, E0)
-    grp.sync()
-    barrier(world)
-    t0 = time.perf_counter()
-    rp.run(grp, E0, E1)
-    t_issue = time.perf_counter() - t0  # host time to enqueue the K steps (the GPU runs behind it)
-    grp.sync()
-    barrier(world)
-    dt = max_over_ranks(time.perf_counter() - t0, world, transport)
-    rp.check(0, E1)  # parity with the recorded closed-loop run, every reply byte
+
+    def run_laps(n_epochs):
+        """n_epochs of the timed stretch [E0, E1), in laps of at most E1 - E0 epochs.  Every lap starts from the recording's
+        start (restored), the receive buffers hold the pristine requests again (in-place replay) and the warm-up epochs
+        [0, E0) are replayed untimed -- before the clock starts.  Returns (seconds, host issue seconds, txns, requests,
+        epochs of the last lap) of the laps' timed stretches; a run of at most MAX_TIMED_STEPS steps is one lap."""
+        sec = issue = 0.0
+        tx = n_ops = m = 0
+        while n_epochs > 0:
+            m = min(n_epochs, E1 - E0)
+            grp.restore()
+            rp.reset()
+            rp.run(grp, 0, E0)
+            grp.sync()
+            barrier(world)
+            t0 = time.perf_counter()
+            rp.run(grp, E0, E0 + m)
+            issue += time.perf_counter() - t0  # host time to enqueue the steps (the GPU runs behind it)
+            grp.sync()
+            barrier(world)
+            sec += max_over_ranks(time.perf_counter() - t0, world, transport)
+            tx, n_ops, n_epochs = tx + sum(done[E0:E0 + m]), n_ops + rp.ops(E0, E0 + m), n_epochs - m
+        return sec, issue, tx, n_ops, m
+
+    if W * B > E0:  # warm-up steps beyond the recorded warm-up epochs: laps of the timed stretch, untimed
+        run_laps(W * B - E0)
+    dt, t_issue, txns_rank, ops_rank, m_last = run_laps(K * B)
+    rp.check(0, E0 + m_last)  # parity with the recorded closed-loop run, every reply byte
+    if args.dump_outputs and rank == 0:  # the replies of the last timed step, before any other leg replays the trace
+        dump_replies(args.dump_outputs, rp, E0 + m_last - B, E0 + m_last)
     overflow = grp.router.overflow() if grp.router is not None else 0
     ref = shipped = None
-    compact = getattr(args, "compact", False)
+    compact, lean = getattr(args, "compact", False), getattr(args, "lean", False)
     if kind == "tatp" and world == 1 and not (args.no_cpu_baseline or args.no_cpu_reference or compact):
         from oracle import oracle as orc  # cpu_baseline leg only: the reference populates (minutes, one host core)
         if orc.ref_available("tatp"):     # while the remaining GPU legs run; the headline region above is over
@@ -1188,38 +1354,30 @@ def bench_txn(args, world, rank, dev, transport, kind):
             except Exception:
                 shipped = None
 
-    txns = sum_over_ranks(sum(done[E0:E1]), world, transport)
-    ops = sum_over_ranks(rp.ops(E0, E1), world, transport)
+    txns = sum_over_ranks(txns_rank, world, transport)
+    ops = sum_over_ranks(ops_rank, world, transport)
     value = txns / dt / 1e6
 
     # run-to-run spread of the same K steps (state restored before each)
     repeats = []
-    for _ in range(0 if compact else 4):
-        grp.restore()
-        rp.reset()
-        rp.run(grp, 0, E0)
-        grp.sync()
-        barrier(world)
-        t1 = time.perf_counter()
-        rp.run(grp, E0, E1)
-        grp.sync()
-        barrier(world)
-        repeats.append(txns / max_over_ranks(time.perf_counter() - t1, world, transport) / 1e6)
+    for _ in range(0 if compact or lean else 4):
+        repeats.append(txns / run_laps(K * B)[0] / 1e6)
 
     # per-epoch latency, device side: submit of the three batches -> all replies visible in HBM
-    grp.restore()
-    rp.reset()
     lat = []
-    for e in range(min(E1, 120)):
-        grp.sync()
-        t = time.perf_counter()
-        rp.run(grp, e, e + 1)
-        grp.sync()
-        lat.append((time.perf_counter() - t) * 1e6)
+    if not lean:
+        grp.restore()
+        rp.reset()
+        for e in range(min(E1, 120)):
+            grp.sync()
+            t = time.perf_counter()
+            rp.run(grp, e, e + 1)
+            grp.sync()
+            lat.append((time.perf_counter() - t) * 1e6)
     lat = np.array(lat[min(E0, len(lat) // 2):])
 
     roof, extra = None, {}
-    if world == 1 and grp.router is None:
+    if world == 1 and grp.router is None and not lean:
         grp.restore()
         rp.reset()
         for e in grp.engines:
@@ -1470,7 +1628,7 @@ def bench_txn(args, world, rank, dev, transport, kind):
                    "closed_loop_Mtxn_s": closed["value"] if closed else None,
                    "value_pcie_Mtxn_s": host.get("value_pcie"),
                    "latency_p50_us": pct(lat, 50), "latency_p99_us": pct(lat, 99)},
-        "Mops_s": round(ops / dt / 1e6, 3), "ops_per_txn": round(ops / max(1.0, txns), 3), "ms_per_epoch": round(dt / (E1 - E0) * 1e3, 5),
+        "Mops_s": round(ops / dt / 1e6, 3), "ops_per_txn": round(ops / max(1.0, txns), 3), "ms_per_epoch": round(dt / (K * B) * 1e3, 5),
         # the reference client's two rates (tatp/caladan/client_udp_shard.cc:102-103): throughput = finished
         # transactions, goodput = committed ones (a NOT_EXIST read of a row the population never made counts as not
         # committed there too)
@@ -1495,7 +1653,7 @@ def client_sweep(args, world, rank, dev, transport, kind):
     rows = []
     for c in (4096, 32768, 131072, 524288, 1048576, 2097152):  # (2M clients: ~0.97M requests per shard server and epoch -- one pass still)
         a = copy.copy(args)
-        a.clients, a.compact, a.steps, a.warmup, a.per_step = c, True, 6, 2, 8
+        a.clients, a.compact, a.steps, a.warmup, a.per_step, a.dump_outputs = c, True, 6, 2, 8, None
         a.no_cpu_baseline = a.no_rand64 = a.no_closed_loop = a.no_host_path = True
         r = bench_txn(a, world, rank, dev, transport, kind)
         gc.collect()
@@ -1517,6 +1675,7 @@ def other_workloads(args, world, rank, dev, transport):
     for wl in ("tatp_nurand", "tatp_1m_clients", "tatp_2m_clients", "fasst", "fasst_36m", "2pl", "log", "store", "smallbank"):
         a = copy.copy(args)
         a.workload, a.compact, a.steps, a.warmup, a.per_step, a.theta = wl, True, 8, 2, (4 if wl in ("store", "smallbank", "tatp_nurand") else 16), None
+        a.dump_outputs = None
         if wl in ("tatp_1m_clients", "tatp_2m_clients"):  # the headline at twice / four times the clients (the r03 sweep was still rising at 524k)
             a.workload, a.clients, a.steps, a.warmup, a.per_step, a.no_cpu_baseline = "tatp", (1 << 20) if wl == "tatp_1m_clients" else (1 << 21), 4, 1, 4, True
         a.no_rand64 = a.no_closed_loop = a.no_host_path = True
@@ -1600,7 +1759,7 @@ def main():
         import copy
 
         a = copy.copy(args)
-        a.force_exchange, a.compact, a.steps, a.warmup = True, True, 8, 2
+        a.force_exchange, a.compact, a.steps, a.warmup, a.dump_outputs = True, True, 8, 2, None
         a.no_rand64 = a.no_closed_loop = a.no_host_path = a.no_cpu_baseline = True
         try:
             r = run_workload(a, world, rank, dev, transport)

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def main():
     d = "/tmp/prof_fx"
     subprocess.run(["rm", "-rf", d])
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-exchange", "--steps", "6", "--warmup", "1", "--no-cpu-baseline", "--no-rand64",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-exchange", "--steps", "6", "--warmup", "1", "--no-cpu-baseline", "--no-rand64",
             "--no-host-path", "--no-closed-loop", "--no-other-workloads", "--no-shim", "--no-exchange-leg", "--no-as-shipped"] + sys.argv[1:]
     r = subprocess.run(["rocprofv3", "--kernel-trace", "--memory-copy-trace", "-d", d, "-o", "fx", "--"] + base, cwd="/tmp",
                        env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True, timeout=900)

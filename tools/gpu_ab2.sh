@@ -3,7 +3,7 @@
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT"
-ARGS=${AB_ARGS:---no-cpu-baseline --no-rand64 --no-host-path --no-closed-loop}
+ARGS=${AB_ARGS:---full --no-cpu-baseline --no-rand64 --no-host-path --no-closed-loop}
 N=${AB_N:-3}
 P='import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d.get("kernels_us"), d.get("value_repeats"))'
 for i in $(seq 1 $N); do

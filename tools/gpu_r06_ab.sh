@@ -11,7 +11,7 @@ WL=$1; shift
 if [ -n "${AB_TESTS:-}" ]; then echo "== $AB_TESTS"; timeout 1800 python -m pytest $AB_TESTS -x -q 2>&1 | tail -5; fi
 for spec in "$@"; do
   name=${spec%%:*}; envs=${spec#*:}
-  env ${envs//;/ } timeout 900 python bench.py --workload $WL --legs headline ${AB_ARGS:-} > "$OUT/$name.json" 2> "$OUT/$name.err"
+  env ${envs//;/ } timeout 900 python bench.py --full --workload $WL --legs headline ${AB_ARGS:-} > "$OUT/$name.json" 2> "$OUT/$name.err"
   python - <<PY
 import json
 try:

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 echo "== gpu suite"; timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -12
 echo "== smoke"; timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1
-echo "== default line"; timeout 1500 python bench.py > "$OUT/bench_tatp.json" 2> "$OUT/bench_tatp.err"; echo "rc $?"
+echo "== default line"; timeout 1500 python bench.py --full > "$OUT/bench_tatp.json" 2> "$OUT/bench_tatp.err"; echo "rc $?"
 python - <<PY
 import json
 d = json.loads(open("$OUT/bench_tatp.json").read().strip().splitlines()[-1])

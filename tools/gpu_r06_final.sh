@@ -22,7 +22,7 @@ for wl in ${PROFILE_WL:-tatp store smallbank fasst 2pl log}; do
 done
 line() {  # name, args...
   name=$1; shift
-  timeout 1800 python bench.py "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"
+  timeout 1800 python bench.py --full "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"
   python - <<PY
 import json
 try:

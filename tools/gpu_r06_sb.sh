@@ -6,7 +6,7 @@ timeout 900 python -m pytest tests/test_gpu_kv.py tests/test_gpu_ahead.py -k sma
 for m in "$@"; do
   echo "== SB_SPLIT_MIN $m"
   DINT_KV_SB_SPLIT_MIN=$m timeout 300 python tools/exp_sb_tail.py 200 2>&1 | grep -v "engine\|amdgpu" | cut -c1-100 | head -6
-  DINT_KV_SB_SPLIT_MIN=$m timeout 300 python bench.py --workload smallbank --legs headline 2>/dev/null | python -c "
+  DINT_KV_SB_SPLIT_MIN=$m timeout 300 python bench.py --full --workload smallbank --legs headline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['value_repeats'], d['kernels_us'], d['latency_us']['p50'], d['latency_us']['p99'], d['late'])"
 done

@@ -18,7 +18,7 @@ def main():
     wl = sys.argv[1] if len(sys.argv) > 1 else "tatp"
     d = "/tmp/prof_gaps"
     subprocess.run(["rm", "-rf", d])
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--legs", "headline", "--steps", "6", "--warmup", "2"] + sys.argv[2:]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", wl, "--legs", "headline", "--steps", "6", "--warmup", "2"] + sys.argv[2:]
     r = subprocess.run(["rocprofv3", "--kernel-trace", "-d", d, "-o", "gaps", "--"] + base, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"),
                        capture_output=True, text=True, timeout=900)
     out = [f"# rc {r.returncode}"]

@@ -60,7 +60,7 @@ def main():
     steps, warm, per_step = 12, 1, 16  # 208 passes per engine; bench.py's event-timed replay runs <= 200 of them last
     engines = 3 if wl in ("tatp", "smallbank") else 1
     last = engines * 190  # ... of which the last 190 per engine are averaged here
-    base = [sys.executable, os.path.join(ROOT, "bench.py")] + rest + ["--steps", str(steps), "--warmup", str(warm), "--per-step", str(per_step),
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + rest + ["--steps", str(steps), "--warmup", str(warm), "--per-step", str(per_step),
                                                                        "--legs", "headline"]
     env = dict(os.environ, TMPDIR="/tmp")
     passes = [("trace", ["--kernel-trace", "--stats"]), ("FETCH_SIZE", ["--pmc", "FETCH_SIZE", "--kernel-trace"]),

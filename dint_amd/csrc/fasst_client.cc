@@ -18,84 +18,53 @@
 // workers are ~320 transactions each).
 #include <string.h>
 
-#include <algorithm>
 #include <new>
 #include <vector>
 
 #include "../../include/dint_abi.h"
 #include "../../include/dint_driver.h"
-#include "zipf_table.h"
+#include "lock_clients.h"
 
-namespace {
-
-#pragma pack(push, 1)
-struct FasstMsg {  // lock_fasst/caladan/proto.h:31-36 (= lock_fasst/udp/net.h:23-29)
-  uint8_t type;
-  uint32_t lid;
-  uint32_t ver;
-};
-#pragma pack(pop)
-static_assert(sizeof(FasstMsg) == 9, "packed wire struct");
-
-enum : uint8_t { F_READ = 0, F_ACQ = 1, F_ABORT = 2, F_COMMIT = 3, F_GRANT_READ = 4, F_GRANT_LOCK = 5, F_REJECT_LOCK = 6 };
-enum : uint8_t { P_READ, P_ACQ, P_REJ_ABORT, P_VALIDATE, P_RB_ABORT, P_COMMIT };
-
-struct Worker {
-  uint64_t rng;
-  uint32_t keys[10], vers[10], wkeys[10];
-  uint8_t nk, nw, phase, pos, abort_n;
-};
-
-}  // namespace
-
+// The worker state machine lives in lock_clients.h (shared with the GPU-resident client, k_lock_client.hip); this file
+// is its host loop over the workers.
 struct dint_fasst_client {
   dint_fasst_client_config cfg{};
   dint_fasst_client_stats st{};
-  std::vector<Worker> w;
+  std::vector<LcWorker> w;
   std::vector<FasstMsg> out;
   ZipfTable zipf;
+  LcParams P{};
   bool awaiting = false;
-
-  uint32_t rnd(Worker &x) {  // fastrand
-    x.rng = x.rng * 1103515245ull + 12345ull;
-    return (uint32_t)(x.rng >> 32);
-  }
-  uint32_t pick(Worker &x) {
-    if (cfg.key_dist == 1) return (uint32_t)zipf_lookup(zipf.cdf.data(), zipf.n, rnd(x));
-    return (uint32_t)(((uint64_t)rnd(x) * cfg.key_space) >> 32);  // uniform over [0, key_space)
-  }
-  void new_txn(Worker &x) {  // trace_init.sh:12-27
-    x.nk = (uint8_t)(5 + rnd(x) % 6);
-    for (uint8_t i = 0; i < x.nk;) {  // distinct keys (random.sample)
-      const uint32_t k = pick(x);
-      bool dup = false;
-      for (uint8_t j = 0; j < i; j++) dup |= x.keys[j] == k;
-      if (!dup) x.keys[i++] = k;
-    }
-    std::sort(x.keys, x.keys + x.nk);
-    x.nw = 0;
-    for (uint8_t i = 0; i < x.nk; i++)
-      if (rnd(x) % 100 >= cfg.read_pct) x.wkeys[x.nw++] = x.keys[i];
-    x.phase = P_READ;
-    x.pos = 0;
-  }
-  void restart(Worker &x) { x.phase = P_READ; x.pos = 0; }
 };
+
+// the config check and the key distribution, shared with the 2PL host client (tpl_client.cc) and the GPU client
+int dint_lock_client_params(const dint_fasst_client_config *cfg, LcParams *P, ZipfTable *zipf) {
+  if (!cfg || cfg->n_workers == 0 || cfg->key_space < 16 || cfg->read_pct > 100 || cfg->key_dist > 1) return DINT_EINVAL;
+  if (cfg->key_dist == 1 && !(cfg->zipf_theta > 0 && cfg->zipf_theta < 1)) return DINT_EINVAL;
+  *P = LcParams{cfg->key_space, cfg->read_pct, cfg->key_dist, 0, cfg->key_space, nullptr};
+  if (cfg->key_dist == 1) {
+    zipf->init(cfg->key_space, cfg->zipf_theta);
+    P->zipf_cdf = zipf->cdf.data();
+  }
+  return 0;
+}
 
 extern "C" {
 
 int dint_fasst_client_create(const dint_fasst_client_config *cfg, dint_fasst_client_t **out) {
-  if (!cfg || !out || cfg->n_workers == 0 || cfg->key_space < 16 || cfg->read_pct > 100 || cfg->key_dist > 1) return DINT_EINVAL;
-  if (cfg->key_dist == 1 && !(cfg->zipf_theta > 0 && cfg->zipf_theta < 1)) return DINT_EINVAL;
+  if (!cfg || !out) return DINT_EINVAL;
   try {
     dint_fasst_client *c = new dint_fasst_client();
+    if (int rc = dint_lock_client_params(cfg, &c->P, &c->zipf)) {
+      delete c;
+      return rc;
+    }
     c->cfg = *cfg;
     c->w.resize(cfg->n_workers);
     c->out.resize(cfg->n_workers);
-    if (cfg->key_dist == 1) c->zipf.init(cfg->key_space, cfg->zipf_theta);
     for (uint32_t i = 0; i < cfg->n_workers; i++) {
-      c->w[i].rng = 0xdeadbeefull + cfg->first_worker + i;
-      c->new_txn(c->w[i]);
+      c->w[i].r = 0xdeadbeefull + cfg->first_worker + i;
+      c->w[i].hdr = lc_new_txn(c->w[i], c->P);
     }
     *out = c;
   } catch (const std::bad_alloc &) {
@@ -110,15 +79,10 @@ void dint_fasst_client_destroy(dint_fasst_client_t *c) { delete c; }
 const void *dint_fasst_client_next(dint_fasst_client_t *c) {
   if (!c || c->awaiting) return nullptr;
   for (size_t i = 0; i < c->w.size(); i++) {
-    Worker &x = c->w[i];
-    FasstMsg m = {0, 0, 0};
-    switch (x.phase) {
-      case P_READ: case P_VALIDATE: m.type = F_READ; m.lid = x.keys[x.pos]; break;
-      case P_ACQ: m.type = F_ACQ; m.lid = x.wkeys[x.pos]; break;
-      case P_REJ_ABORT: case P_RB_ABORT: m.type = F_ABORT; m.lid = x.wkeys[x.pos]; break;
-      default: m.type = F_COMMIT; m.lid = x.wkeys[x.pos]; break;
-    }
-    c->out[i] = m;
+    const LcWorker &x = c->w[i];
+    uint8_t type;
+    const uint32_t j = lc_fasst_req(x.hdr, &type);
+    c->out[i] = FasstMsg{type, x.keys[j], 0};
   }
   c->st.requests += c->w.size();
   c->st.epochs++;
@@ -131,46 +95,14 @@ int dint_fasst_client_consume(dint_fasst_client_t *c, const void *replies) {
   if (!c->awaiting) return DINT_ESTATE;
   const FasstMsg *rep = (const FasstMsg *)replies;
   for (size_t i = 0; i < c->w.size(); i++) {
-    Worker &x = c->w[i];
+    LcWorker &x = c->w[i];
     const FasstMsg r = rep[i];
-    if (r.lid != c->out[i].lid) c->st.protocol_errors++;  // the asserts of client.cc:205-206,241-242
-    switch (x.phase) {
-      case P_READ:  // :237-245
-        if (r.type != F_GRANT_READ) c->st.protocol_errors++;
-        x.vers[x.pos] = r.ver;
-        if (++x.pos == x.nk) { x.pos = 0; x.phase = x.nw ? P_ACQ : P_VALIDATE; }
-        break;
-      case P_ACQ:  // :248-270
-        if (r.type == F_GRANT_LOCK) {
-          if (++x.pos == x.nw) { x.pos = 0; x.phase = P_VALIDATE; }
-        } else if (r.type == F_REJECT_LOCK) {
-          c->st.rejects++;
-          if (x.pos) { x.abort_n = x.pos; x.pos = 0; x.phase = P_REJ_ABORT; }
-          else c->restart(x);
-        } else {
-          c->st.protocol_errors++;  // "received wrong packet"
-        }
-        break;
-      case P_REJ_ABORT:
-        if (++x.pos == x.abort_n) c->restart(x);
-        break;
-      case P_VALIDATE:  // :196-213
-        if (r.ver != x.vers[x.pos]) {
-          c->st.rollbacks++;
-          if (x.nw) { x.pos = 0; x.phase = P_RB_ABORT; }
-          else c->restart(x);
-        } else if (++x.pos == x.nk) {
-          if (x.nw) { x.pos = 0; x.phase = P_COMMIT; }
-          else { c->st.committed++; c->new_txn(x); }
-        }
-        break;
-      case P_RB_ABORT:  // :215-222
-        if (++x.pos == x.nw) c->restart(x);
-        break;
-      default:  // P_COMMIT :224-229
-        if (++x.pos == x.nw) { c->st.committed++; c->new_txn(x); }
-        break;
-    }
+    uint32_t ev;
+    x.hdr = lc_fasst_consume(x, x.hdr, c->P, r.type, r.lid, r.ver, &ev);
+    c->st.committed += (ev & LC_EV_COMMIT) != 0;
+    c->st.rejects += (ev & LC_EV_REJECT) != 0;
+    c->st.rollbacks += (ev & LC_EV_ROLLBACK) != 0;
+    c->st.protocol_errors += ((ev & LC_EV_PERR_LID) != 0) + ((ev & LC_EV_PERR_TYPE) != 0);
   }
   c->awaiting = false;
   return 0;
@@ -182,11 +114,13 @@ int dint_fasst_client_consume(dint_fasst_client_t *c, const void *replies) {
 int dint_fasst_client_peek(const dint_fasst_client_t *c, uint32_t worker, uint32_t *keys, uint32_t *n_keys, uint32_t *wkeys,
                            uint32_t *n_wkeys) {
   if (!c || !keys || !n_keys || !wkeys || !n_wkeys || worker >= c->w.size()) return DINT_EINVAL;
-  const Worker &x = c->w[worker];
-  *n_keys = x.nk;
-  *n_wkeys = x.nw;
-  memcpy(keys, x.keys, sizeof(uint32_t) * x.nk);
-  memcpy(wkeys, x.wkeys, sizeof(uint32_t) * x.nw);
+  const LcWorker &x = c->w[worker];
+  const LcState s = lc_unpack(x.hdr);
+  *n_keys = s.nk;
+  *n_wkeys = 0;
+  memcpy(keys, x.keys, sizeof(uint32_t) * s.nk);
+  for (uint32_t j = 0; j < s.nk; j++)
+    if ((s.wmask >> j) & 1u) wkeys[(*n_wkeys)++] = x.keys[j];
   return 0;
 }
 

@@ -240,6 +240,136 @@ class FasstClient:
         return {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
 
 
+class TplClientStats(C.Structure):
+    _fields_ = [("requests", C.c_uint64), ("epochs", C.c_uint64), ("committed", C.c_uint64), ("rejects", C.c_uint64),
+                ("protocol_errors", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class LcgTplClient:
+    """The lock_2pl load generator in C (lock_2pl/caladan/client.cc:167-240 restated, csrc/tpl_client.cc): W workers in
+    lock step that draw their transactions exactly as :class:`FasstClient` does (the reference's LCG seeded 0xdeadbeef +
+    worker), with :class:`TplClient`'s state machine -- so the GPU-resident client (:class:`GpuLockClient`) can reproduce
+    its stream.  ``next()`` = one 6-byte request per worker, ``consume(replies)`` advances them."""
+
+    def __init__(self, n_workers: int = 4096, key_space: int = 24_000_000, *, read_pct: int = 80,
+                 zipf_theta: float | None = 0.8, first_worker: int = 0):
+        from .wire import TPL_MSG
+
+        L = self._L = _lib.load()
+        vp = C.c_void_p
+        L.dint_tpl_client_create.restype, L.dint_tpl_client_create.argtypes = C.c_int, [C.POINTER(FasstClientConfig), C.POINTER(vp)]
+        L.dint_tpl_client_destroy.restype, L.dint_tpl_client_destroy.argtypes = None, [vp]
+        L.dint_tpl_client_next.restype, L.dint_tpl_client_next.argtypes = vp, [vp]
+        L.dint_tpl_client_consume.restype, L.dint_tpl_client_consume.argtypes = C.c_int, [vp, vp]
+        L.dint_tpl_client_get_stats.restype, L.dint_tpl_client_get_stats.argtypes = C.c_int, [vp, C.POINTER(TplClientStats)]
+        L.dint_tpl_client_peek.restype, L.dint_tpl_client_peek.argtypes = C.c_int, [vp, C.c_uint32, vp, vp, vp]
+        self.dtype, self.n = TPL_MSG, n_workers
+        cfg = FasstClientConfig(n_workers=n_workers, first_worker=first_worker, key_space=key_space, read_pct=read_pct,
+                                key_dist=0 if zipf_theta is None else 1, zipf_theta=zipf_theta or 0.0)
+        h = vp()
+        _lib.check(L.dint_tpl_client_create(C.byref(cfg), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dint_tpl_client_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if not sys.is_finalizing():
+            self.close()
+
+    def next(self) -> np.ndarray:
+        p = self._L.dint_tpl_client_next(self._h)
+        if not p:
+            raise _lib.DintError("dint_tpl_client_next: replies of the previous epoch are still outstanding")
+        return np.frombuffer((C.c_uint8 * (self.n * 6)).from_address(p), self.dtype).copy()
+
+    def consume(self, replies: np.ndarray):
+        replies = np.ascontiguousarray(replies)
+        _lib.check(self._L.dint_tpl_client_consume(self._h, replies.ctypes.data))
+
+    def peek(self, worker: int = 0):
+        """(lids in ascending order, their types: 1 = exclusive) of the transaction `worker` is running"""
+        lid, typ, n = (C.c_uint32 * 10)(), (C.c_uint8 * 10)(), C.c_uint32()
+        _lib.check(self._L.dint_tpl_client_peek(self._h, worker, lid, typ, C.byref(n)))
+        return list(lid[:n.value]), list(typ[:n.value])
+
+    def stats(self) -> dict:
+        s = TplClientStats()
+        _lib.check(self._L.dint_tpl_client_get_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+
+
+class LockClientConfig(C.Structure):
+    """dint_lock_client_config (include/dint_driver.h): FasstClientConfig with the workload where it has reserved0"""
+    _fields_ = [("n_workers", C.c_uint32), ("first_worker", C.c_uint32), ("key_space", C.c_uint32),
+                ("read_pct", C.c_uint32), ("key_dist", C.c_uint32), ("workload", C.c_uint32),
+                ("zipf_theta", C.c_double), ("reserved", C.c_uint32 * 8)]
+
+
+class GpuLockClient:
+    """The lock_fasst / lock_2pl load generator resident on the GPU (csrc/k_lock_client.hip, include/dint_driver.h
+    dint_lock_gclient_*): the workers of :class:`FasstClient` / :class:`LcgTplClient`, one lane each.  ``next(stream)``
+    emits the epoch's ``n`` requests (request i = worker i) into a device buffer (``batch_ptr``, refreshed by every
+    ``next``: two buffers alternate), the lock server answers in place, ``consume(stream)`` feeds the replies back (on the
+    stream of ``next``: fused into the next emit kernel).  The request stream is bit-identical to the host client's."""
+
+    def __init__(self, workload: Workload, n_workers: int = 4096, key_space: int = 24_000_000, *, read_pct: int = 80,
+                 zipf_theta: float | None = 0.8, first_worker: int = 0, device: int = -1):
+        L = self._L = _lib.load()
+        vp = C.c_void_p
+        L.dint_lock_gclient_create.restype, L.dint_lock_gclient_create.argtypes = C.c_int, [C.POINTER(LockClientConfig), C.c_int32, C.POINTER(vp)]
+        L.dint_lock_gclient_destroy.restype, L.dint_lock_gclient_destroy.argtypes = None, [vp]
+        L.dint_lock_gclient_next.restype, L.dint_lock_gclient_next.argtypes = C.c_int, [vp, vp]
+        L.dint_lock_gclient_consume.restype, L.dint_lock_gclient_consume.argtypes = C.c_int, [vp, vp]
+        L.dint_lock_gclient_batch.restype, L.dint_lock_gclient_batch.argtypes = vp, [vp]
+        L.dint_lock_gclient_read_batch.restype, L.dint_lock_gclient_read_batch.argtypes = C.c_int, [vp, vp]
+        L.dint_lock_gclient_get_stats.restype, L.dint_lock_gclient_get_stats.argtypes = C.c_int, [vp, C.POINTER(FasstClientStats)]
+        from .wire import MSG_DTYPE
+
+        self.workload = Workload(workload)
+        self.dtype, self.n = MSG_DTYPE[self.workload], n_workers
+        cfg = LockClientConfig(n_workers=n_workers, first_worker=first_worker, key_space=key_space, read_pct=read_pct,
+                               key_dist=0 if zipf_theta is None else 1, workload=int(workload), zipf_theta=zipf_theta or 0.0)
+        h = vp()
+        _lib.check(L.dint_lock_gclient_create(C.byref(cfg), device, C.byref(h)))
+        self._h = h
+        self.batch_ptr = L.dint_lock_gclient_batch(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dint_lock_gclient_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        # at interpreter exit the HIP runtime may already be gone (module teardown order): the process is ending anyway
+        if not sys.is_finalizing():
+            self.close()
+
+    def next(self, stream: int = 0):
+        _lib.check(self._L.dint_lock_gclient_next(self._h, stream))
+        self.batch_ptr = self._L.dint_lock_gclient_batch(self._h)  # the two buffers alternate
+
+    def consume(self, stream: int = 0):
+        _lib.check(self._L.dint_lock_gclient_consume(self._h, stream))
+
+    def read_batch(self) -> np.ndarray:
+        """host copy of the current batch (synchronises; tests and debugging)"""
+        out = np.zeros(self.n, self.dtype)
+        _lib.check(self._L.dint_lock_gclient_read_batch(self._h, out.ctypes.data))
+        return out
+
+    def stats(self) -> dict:
+        """synchronises; lock_2pl has no rollbacks (the key is left out)"""
+        s = FasstClientStats()
+        _lib.check(self._L.dint_lock_gclient_get_stats(self._h, C.byref(s)))
+        d = {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+        if self.workload == Workload.TPL:
+            del d["rollbacks"]
+        return d
+
+
 def fasst_trace(server, n_requests: int = 24_000_000, **kw):
     """The lock_fasst request trace: closed loop of a FasstClient against `server` (an object with
     submit(ndarray) -> ndarray) until n_requests requests were issued.  Returns (requests, replies, client stats);

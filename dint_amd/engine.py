@@ -70,6 +70,7 @@ class Engine:
         _lib.check(self._L.dint_engine_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self.shard_index, self.shard_count = shard_index, max(1, shard_count)
+        self.flags = flags
         self.val_size = 8 if self.workload == Workload.SMALLBANK else 40
         self.pass_max = int(self._L.dint_max_pass(self._h))
 

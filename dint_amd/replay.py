@@ -238,3 +238,36 @@ class GpuLoop:
         for st in self.streams:
             st.synchronize()
         self.g.sync()
+
+
+class LockLoop:
+    """The lock micro-benchmarks' closed loop that never leaves the GPU: a :class:`dint_amd.driver.GpuLockClient` and one
+    lock server (an :class:`Engine` of the same workload).  One epoch = emit kernel -> the engine's passes over the
+    ``n`` requests, answered IN PLACE in the client's batch (the lock path takes d_replies == d_reqs: its count stage
+    copies request to reply only when they differ) -> consume, fused into the next epoch's emit kernel.  No host round
+    trip, no PCIe.  An epoch of more requests than the engine's ``pass_max`` (65,536 by default) is split into passes by
+    the engine itself, in request order.
+
+    The batch is written by the client's kernel on the same stream right before the submission, so the promise of
+    DINT_FLAG_INPUTS_READY (request bytes complete in device memory when the call is made) does NOT hold: the engine must
+    run without that flag, and the calls are plain stream-ordered dint_submit_device (no look-ahead either: the next
+    batch depends on these replies)."""
+
+    def __init__(self, engine: Engine, gclient):
+        from ._lib import FLAG_INPUTS_READY
+
+        assert engine.workload == gclient.workload, "the client's workload must be the engine's"
+        assert not (engine.flags & FLAG_INPUTS_READY), "the closed loop cannot keep DINT_FLAG_INPUTS_READY's promise"
+        self.e, self.c = engine, gclient
+        self.stream = torch.cuda.Stream()
+
+    def epochs(self, n: int) -> None:
+        xs, e, c = self.stream.cuda_stream, self.e, self.c
+        for _ in range(n):
+            c.next(xs)
+            e.submit_device(c.batch_ptr, c.n, c.batch_ptr, xs)
+            c.consume(xs)
+
+    def sync(self):
+        self.stream.synchronize()
+        self.e.sync()

@@ -123,6 +123,56 @@ int dint_fasst_client_get_stats(const dint_fasst_client_t *c, dint_fasst_client_
 int dint_fasst_client_peek(const dint_fasst_client_t *c, uint32_t worker, uint32_t *keys, uint32_t *n_keys, uint32_t *wkeys,
                            uint32_t *n_wkeys);
 
+/* ---- lock_2pl load generator ------------------------------------------------------------------------------
+ * lock_2pl/caladan/client.cc:167-240 (ClientLoop) over transactions shaped like lock_2pl/caladan/trace_init.sh:6-27,
+ * W workers in lock step, one outstanding request each.  A worker draws its transactions exactly as the lock_fasst
+ * worker does (same config: seed 0xdeadbeef + first_worker + i, 5..10 distinct sorted keys, a key is an exclusive lock
+ * iff rnd % 100 >= read_pct); it acquires the locks in ascending order, on REJECT with locks held releases them in
+ * acquisition order and tries the same transaction again, on REJECT with nothing held sends the same ACQUIRE again, and
+ * once every lock is held releases them in reverse order (the transaction has committed).  next / consume as
+ * dint_fasst_client_*, 6-byte messages. */
+typedef struct dint_tpl_client dint_tpl_client_t;
+typedef struct dint_tpl_client_stats {
+  uint64_t requests, epochs;
+  uint64_t committed;        /* transactions whose locks were all granted (and released) */
+  uint64_t rejects;          /* REJECT replies to an ACQUIRE */
+  uint64_t protocol_errors;  /* an ACQUIRE answered with neither GRANT nor REJECT, a RELEASE without RELEASE_ACK */
+  uint64_t reserved[3];
+} dint_tpl_client_stats;
+int dint_tpl_client_create(const dint_fasst_client_config *cfg, dint_tpl_client_t **out);
+void dint_tpl_client_destroy(dint_tpl_client_t *c);
+const void *dint_tpl_client_next(dint_tpl_client_t *c);  /* NULL while the replies of the last epoch are outstanding */
+int dint_tpl_client_consume(dint_tpl_client_t *c, const void *replies);
+int dint_tpl_client_get_stats(const dint_tpl_client_t *c, dint_tpl_client_stats *out);
+/* the transaction `worker` is running: lids[0 .. *n_locks) in ascending order, types[] 1 = exclusive (room for 10 each) */
+int dint_tpl_client_peek(const dint_tpl_client_t *c, uint32_t worker, uint32_t *lids, uint8_t *types, uint32_t *n_locks);
+
+/* ---- the lock load generators, resident on the GPU ---------------------------------------
+ * The lock_fasst or lock_2pl workers of the host clients above, one lane per worker, state in HBM.  dint_lock_gclient_next
+ * launches a kernel in which every worker emits its next request: request i belongs to worker i, so the batch is
+ * n_workers messages in worker order -- bit-identical to the host client's.  The lock server answers IN PLACE
+ * (dint_submit_device(engine, dint_lock_gclient_batch(c), n_workers, same pointer, stream)); dint_lock_gclient_consume
+ * makes every worker take its reply -- in a kernel of its own, or, when issued on the stream of the last
+ * dint_lock_gclient_next (the closed loop), fused into the next emit kernel: the epoch's batch alternates between two
+ * buffers, so ask dint_lock_gclient_batch again after every next, and keep that stream alive until then
+ * (DINT_LOCK_CLIENT_FUSE=0: always a kernel of its own).  Nothing crosses PCIe. */
+typedef struct dint_lock_gclient dint_lock_gclient_t;
+typedef struct dint_lock_client_config { /* dint_fasst_client_config with the workload where it has reserved0 */
+  uint32_t n_workers, first_worker, key_space, read_pct, key_dist;
+  uint32_t workload; /* DINT_WL_FASST or DINT_WL_2PL */
+  double zipf_theta;
+  uint32_t reserved[8];
+} dint_lock_client_config;
+int dint_lock_gclient_create(const dint_lock_client_config *cfg, int32_t device, dint_lock_gclient_t **out);
+void dint_lock_gclient_destroy(dint_lock_gclient_t *c);
+int dint_lock_gclient_next(dint_lock_gclient_t *c, void *stream);    /* DINT_ESTATE while the last epoch is not consumed */
+int dint_lock_gclient_consume(dint_lock_gclient_t *c, void *stream); /* DINT_ESTATE without a next before it */
+void *dint_lock_gclient_batch(dint_lock_gclient_t *c);               /* device pointer: the CURRENT epoch's n_workers messages */
+/* tests / debugging: synchronise and copy the current batch (n_workers messages) to the host */
+int dint_lock_gclient_read_batch(dint_lock_gclient_t *c, void *host);
+/* synchronises the device (a consume deferred into the next emit runs now); rollbacks stay 0 for lock_2pl */
+int dint_lock_gclient_get_stats(dint_lock_gclient_t *c, dint_fasst_client_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DINT_LIB_PATH") or os.path.join(HERE, "libdint.so")  # (DINT_LIB_PATH: same-box A/B runs of two builds, tools/)
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 #: dint_config.flags (include/dint_abi.h)
 FLAG_KV_ROUNDS, FLAG_COPY_STREAMS, FLAG_LOCK_SAME_KEY, FLAG_KV_NO_HOT, FLAG_INPUTS_READY = 1, 2, 4, 8, 16
 MICRO_BATCH = 65536
@@ -26,6 +26,7 @@ SYMBOLS = [
     "dint_stream_wait", "dint_stream_signal", "dint_route_pack", "dint_route_unpack", "dint_submit_segments",
     "dint_log_drain", "dint_refuse", "dint_route_pack_multi", "dint_route_unpack_multi", "dint_bench_access", "dint_selftest",
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
+    "dint_log_drain_device", "dint_log_apply_device",
 ]
 
 
@@ -52,6 +53,12 @@ class Stats(C.Structure):
         ("route_overflow", C.c_uint64), ("big_bin_requests", C.c_uint64), ("late_requests", C.c_uint64),
         ("reserved", C.c_uint64 * 3),
     ]
+
+
+class ApplyStats(C.Structure):
+    """dint_apply_stats (include/dint_abi.h)"""
+    _fields_ = [("applied", C.c_uint64), ("commits", C.c_uint64), ("inserts", C.c_uint64), ("deletes", C.c_uint64),
+                ("chunks", C.c_uint64), ("reserved", C.c_uint64 * 3)]
 
 
 class DintError(RuntimeError):
@@ -129,6 +136,10 @@ def load() -> C.CDLL:
         "dint_submit_segments_multi_ahead": (C.c_int, [C.POINTER(SegmentsItem), u32, C.POINTER(SegmentsItem), vp]),
         "dint_log_drain": (i64, [vp, vp, u64, C.POINTER(u64)]),
         "dint_refuse": (C.c_int, [u32, vp, u32, vp]),
+        "dint_log_drain_device": (i64, [vp, vp, u64, C.POINTER(u64), vp]),
+        "dint_log_apply_device": (C.c_int, [vp, vp, u64, u32, C.POINTER(ApplyStats)]),
+        # include/dint_driver.h: the replay's classification rule on the host (no device call)
+        "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)  # AttributeError here = the .so does not export the ABI

@@ -111,3 +111,29 @@ struct dint_log {
 };
 void dint_launch_log(const void *d_req, void *d_rep, uint32_t n, dint_log log, dint_scratch s, hipStream_t st,
                      hipEvent_t *ev);
+
+// ---- log replay: k_replay.hip (dint_log_apply_device) -------------------------------------------------------
+// scratch of one chunk of `cap` records; allocated on first use, grown when a call asks for a longer chunk
+struct dint_replay_scratch {
+  uint32_t cap;                  // records a chunk holds at most (0 = nothing allocated)
+  uint64_t *row_in, *row_out;    // [cap] sort key of record i (log_replay.h lr_row) / the keys sorted
+  uint32_t *idx_in, *idx_out;    // [cap] i / the record index at sorted position p: equal rows keep log order
+  uint32_t *slot;                // [cap] sorted position p -> where its READ sits in the probe batch (first record of a row only)
+  uint8_t *types;                // [cap] the request type chosen for record i
+  void *sort_tmp;                // the radix sort's temporary storage
+  size_t sort_tmp_bytes;
+  uint8_t *probe;                // [max(cap, 2)] 55-byte messages: one READ per distinct row of the chunk, answered in place
+  uint8_t *msgs;                 // [cap] the chunk's backup operations in log order, answered in place
+  uint32_t *probe_n;             // device word: READs in the probe batch
+  unsigned long long *counts;    // device words {commits, inserts, deletes} acked
+};
+// bytes of temporary storage the sort of m pairs needs (no GPU work); negative = error
+int64_t dint_replay_sort_bytes(uint32_t m, hipStream_t st);
+// tatp, records [0, m) of a chunk: keys + stable sort + the probe batch (s.probe, *s.probe_n READs); false = the sort failed
+bool dint_launch_replay_group(const void *d_rec, uint32_t m, dint_replay_scratch s, hipStream_t st);
+// tatp, after the replica answered the probe batch in place: the request types, then the messages in log order into s.msgs
+void dint_launch_replay_emit(const void *d_rec, uint32_t m, dint_replay_scratch s, hipStream_t st);
+// smallbank: every record is a COMMIT_BCK, straight into s.msgs
+void dint_launch_replay_emit_sb(const void *d_rec, uint32_t m, dint_replay_scratch s, hipStream_t st);
+// after the replica answered s.msgs in place: the acks by type into s.counts
+void dint_launch_replay_count(uint32_t workload, uint32_t m, dint_replay_scratch s, hipStream_t st);

@@ -126,6 +126,9 @@ struct dint_engine {
   dint_log log{};
   uint64_t log_drained = 0;  // records handed out (or given up as lost) by dint_log_drain
   uint64_t snap_log_drained = 0;  // ... when the snapshot was taken (dint_restore puts it back)
+  // log replay (dint_log_apply_device): scratch of one chunk, allocated on first use; the events of its stage timing
+  dint_replay_scratch replay{};
+  hipEvent_t ev_replay[4] = {};
 
   // kv workloads (store / tatp / smallbank)
   dint_kv kv{};
@@ -487,6 +490,75 @@ int load_rows_locked(dint_engine *e, uint32_t table, const uint64_t *keys, const
   return 0;
 }
 
+// log replay scratch: everything a chunk of `cap` records needs (dint_kernels.h dint_replay_scratch)
+void replay_free(dint_engine *e) {
+  dint_replay_scratch &r = e->replay;
+  hipFree(r.row_in); hipFree(r.row_out); hipFree(r.idx_in); hipFree(r.idx_out); hipFree(r.slot); hipFree(r.types);
+  hipFree(r.sort_tmp); hipFree(r.probe); hipFree(r.msgs); hipFree(r.probe_n); hipFree(r.counts);
+  r = dint_replay_scratch{};
+}
+int replay_alloc(dint_engine *e, uint32_t cap) {
+  dint_replay_scratch &r = e->replay;
+  if (r.cap >= cap) return 0;
+  HIP_TRY(hipStreamSynchronize(e->stream));  // (a replay that still uses the smaller set)
+  replay_free(e);
+  const bool tatp = e->cfg.workload == DINT_WL_TATP;
+  int rc = dev_alloc((void **)&r.msgs, (size_t)cap * e->msg_size + 64, false);
+  if (!rc) rc = dev_alloc((void **)&r.counts, 4 * sizeof(unsigned long long));
+  if (!rc) rc = dev_alloc((void **)&r.probe_n, 4 * sizeof(uint32_t));
+  if (!rc && tatp) {
+    const int64_t tmp = dint_replay_sort_bytes(cap, e->stream);
+    if (tmp < 0) rc = fail(DINT_EHIP, "radix sort: temporary storage query failed");
+    if (!rc) rc = dev_alloc((void **)&r.row_in, (size_t)cap * sizeof(uint64_t), false);
+    if (!rc) rc = dev_alloc((void **)&r.row_out, (size_t)cap * sizeof(uint64_t), false);
+    if (!rc) rc = dev_alloc((void **)&r.idx_in, (size_t)cap * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&r.idx_out, (size_t)cap * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&r.slot, (size_t)cap * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&r.types, cap, false);
+    if (!rc) rc = dev_alloc(&r.sort_tmp, (size_t)tmp, false);
+    if (!rc) rc = dev_alloc((void **)&r.probe, (size_t)std::max(cap, 2u) * e->msg_size + 64, false);
+    r.sort_tmp_bytes = (size_t)std::max<int64_t>(tmp, 0);
+  }
+  if (rc) {
+    replay_free(e);
+    return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());  // (the zero fills ran on the null stream: the engine's stream does not wait for it)
+  r.cap = cap;
+  return 0;
+}
+
+// the records appended since the last drain, oldest first, to host (dint_log_drain) or device memory (dint_log_drain_device):
+// one cursor, one contract
+int64_t log_drain_locked(dint_engine *e, void *records, uint64_t cap, uint64_t *lost, bool to_device, hipStream_t st) {
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());
+  uint32_t t[4];
+  HIP_TRY(hipMemcpy(t, e->log.tail, sizeof t, hipMemcpyDeviceToHost));
+  const uint64_t total = (uint64_t)t[2] | ((uint64_t)t[3] << 32);
+  if (e->log_drained > total) e->log_drained = total;  // the engine was reset / restored to an earlier state
+  uint64_t pending = total - e->log_drained, gone = 0;
+  if (pending > e->log.cap) {  // the ring lapped the reader: the oldest records are overwritten
+    gone = pending - e->log.cap;
+    pending = e->log.cap;
+  }
+  if (lost) *lost = gone;
+  e->log_drained += gone;
+  const uint64_t n = std::min<uint64_t>(pending, cap);
+  uint64_t pos = e->log_drained % e->log.cap;  // record k of the stream lives at ring slot k % cap
+  uint8_t *out = (uint8_t *)records;
+  for (uint64_t done = 0; done < n;) {
+    const uint64_t run = std::min<uint64_t>(n - done, e->log.cap - pos);
+    if (to_device) HIP_TRY(hipMemcpyAsync(out + done * 64, e->log.ring + pos * 64, run * 64, hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(hipMemcpy(out + done * 64, e->log.ring + pos * 64, run * 64, hipMemcpyDeviceToHost));
+    done += run;
+    pos = (pos + run) % e->log.cap;
+  }
+  if (to_device && n) HIP_TRY(hipStreamSynchronize(st));  // the records are complete when the call returns
+  e->log_drained += n;
+  return (int64_t)n;
+}
+
 }  // namespace
 
 extern "C" {
@@ -688,6 +760,9 @@ void dint_engine_destroy(dint_engine_t *e) {
   if (e->s_h2d && e->s_h2d != e->stream) hipStreamDestroy(e->s_h2d);
   if (e->s_d2h && e->s_d2h != e->stream) hipStreamDestroy(e->s_d2h);
   lock_pipe_destroy(e);
+  replay_free(e);
+  for (hipEvent_t ev : e->ev_replay)
+    if (ev) hipEventDestroy(ev);
   hipFree(e->d_lock_tbl);
   hipFree(e->log.ring);
   hipFree(e->log.tail);
@@ -1200,30 +1275,83 @@ int64_t dint_log_drain(dint_engine_t *e, void *records, uint64_t cap, uint64_t *
   if (!e || (cap && !records)) return fail(DINT_EINVAL, "null argument");
   if (!e->log.ring) return fail(DINT_ESTATE, "workload has no log");
   std::lock_guard<std::mutex> lk(e->mu);
+  return log_drain_locked(e, records, cap, lost, false, nullptr);
+}
+
+int64_t dint_log_drain_device(dint_engine_t *e, void *d_records, uint64_t cap, uint64_t *lost, void *stream) {
+  if (!e || (cap && !d_records)) return fail(DINT_EINVAL, "null argument");
+  if (!e->log.ring) return fail(DINT_ESTATE, "workload has no log");
+  std::lock_guard<std::mutex> lk(e->mu);
+  return log_drain_locked(e, d_records, cap, lost, true, stream ? (hipStream_t)stream : e->stream);
+}
+
+int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t chunk, dint_apply_stats *out) {
+  if (!e || (n && !d_records)) return fail(DINT_EINVAL, "null argument");
+  const uint32_t wl = e->cfg.workload;
+  if (wl != DINT_WL_TATP && wl != DINT_WL_SMALLBANK) return fail(DINT_ESTATE, "workload has no table a log replays into");
+  if (e->shard.count > 1) return fail(DINT_EINVAL, "a sharded engine: the log would have to be routed first");
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipDeviceSynchronize());
-  uint32_t t[4];
-  HIP_TRY(hipMemcpy(t, e->log.tail, sizeof t, hipMemcpyDeviceToHost));
-  const uint64_t total = (uint64_t)t[2] | ((uint64_t)t[3] << 32);
-  if (e->log_drained > total) e->log_drained = total;  // the engine was reset / restored to an earlier state
-  uint64_t pending = total - e->log_drained, gone = 0;
-  if (pending > e->log.cap) {  // the ring lapped the reader: the oldest records are overwritten
-    gone = pending - e->log.cap;
-    pending = e->log.cap;
+  if (chunk == 0 || chunk > e->pass_max) chunk = e->pass_max;
+  if (out) memset(out, 0, sizeof *out);
+  if (n == 0) return 0;
+  if (int rc = replay_alloc(e, (uint32_t)std::min<uint64_t>(chunk, n))) return rc;
+  const dint_replay_scratch &r = e->replay;
+  hipStream_t st = e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  HIP_TRY(hipMemsetAsync(r.counts, 0, 4 * sizeof(unsigned long long), st));
+  const bool timed = e->timer.on && out;  // stage times: the stream is drained chunk by chunk (a diagnostic)
+  if (timed)
+    for (hipEvent_t &ev : e->ev_replay)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  double stage_ms[3] = {0, 0, 0};
+  uint64_t chunks = 0;
+  const uint8_t *rec = (const uint8_t *)d_records;
+  for (uint64_t off = 0; off < n; off += chunk, chunks++) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
+    const void *d_rec = rec + off * 64;
+    if (timed) HIP_TRY(hipEventRecord(e->ev_replay[0], st));
+    if (wl == DINT_WL_TATP) {
+      // (the sort's temporary storage was sized for a full chunk; a shorter last chunk never needs more)
+      if (dint_replay_sort_bytes(m, st) > (int64_t)r.sort_tmp_bytes) return fail(DINT_EHIP, "radix sort: temporary storage too small");
+      if (!dint_launch_replay_group(d_rec, m, r, st)) return fail(DINT_EHIP, "radix sort failed");
+      if (timed) HIP_TRY(hipEventRecord(e->ev_replay[1], st));
+      // the READs, answered in place: one segment whose live count is the word k_replay_probe counted in
+      const uint32_t seg_cap = std::max(m, 2u);
+      if (int rc = run_pass(e, r.probe, seg_cap, r.probe, st, 0, dint_seg_view(1, seg_cap, (uint64_t)seg_cap * e->msg_size, r.probe_n, 0)))
+        return rc;
+      e->batches--;  // (not the caller's requests)
+      e->requests -= seg_cap;
+      dint_launch_replay_emit(d_rec, m, r, st);
+    } else {
+      if (timed) HIP_TRY(hipEventRecord(e->ev_replay[1], st));
+      dint_launch_replay_emit_sb(d_rec, m, r, st);
+    }
+    if (timed) HIP_TRY(hipEventRecord(e->ev_replay[2], st));
+    if (int rc = run_pass(e, r.msgs, m, r.msgs, st)) return rc;
+    dint_launch_replay_count(wl, m, r, st);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+    if (timed) {
+      HIP_TRY(hipEventRecord(e->ev_replay[3], st));
+      HIP_TRY(hipEventSynchronize(e->ev_replay[3]));
+      for (int k = 0; k < 3; k++) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e->ev_replay[k], e->ev_replay[k + 1]));
+        stage_ms[k] += ms;
+      }
+    }
   }
-  if (lost) *lost = gone;
-  e->log_drained += gone;
-  const uint64_t n = std::min<uint64_t>(pending, cap);
-  uint64_t pos = e->log_drained % e->log.cap;  // record k of the stream lives at ring slot k % cap
-  uint8_t *out = (uint8_t *)records;
-  for (uint64_t done = 0; done < n;) {
-    const uint64_t run = std::min<uint64_t>(n - done, e->log.cap - pos);
-    HIP_TRY(hipMemcpy(out + done * 64, e->log.ring + pos * 64, run * 64, hipMemcpyDeviceToHost));
-    done += run;
-    pos = (pos + run) % e->log.cap;
-  }
-  e->log_drained += n;
-  return (int64_t)n;
+  if (!out) return 0;
+  HIP_TRY(hipStreamSynchronize(st));
+  unsigned long long c[3];
+  HIP_TRY(hipMemcpy(c, r.counts, sizeof c, hipMemcpyDeviceToHost));
+  out->commits = c[0]; out->inserts = c[1]; out->deletes = c[2];
+  out->applied = c[0] + c[1] + c[2];
+  out->chunks = chunks;
+  for (int k = 0; k < 3; k++) out->reserved[k] = (uint64_t)(stage_ms[k] * 1e6);
+  return 0;
 }
 
 int dint_refuse(uint32_t workload, const void *reqs, uint32_t n, void *replies) {

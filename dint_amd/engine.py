@@ -186,6 +186,26 @@ class Engine:
         n = _lib.check(self._L.dint_log_drain(self._h, rec.ctypes.data, cap, C.byref(lost)))
         return rec[:n], lost.value
 
+    def log_drain_device(self, d_buf, cap: int, stream: int = 0):
+        """dint_log_drain_device: the records appended since the previous drain into the HBM buffer d_buf (cap 64-byte
+        records; a torch uint8 tensor or a device pointer); returns (n, lost).  Shares log_drain's cursor."""
+        lost = C.c_uint64()
+        n = _lib.check(self._L.dint_log_drain_device(self._h, _ptr(d_buf), cap, C.byref(lost), stream))
+        return n, lost.value
+
+    def log_apply_device(self, d_records, n: int, chunk: int = 0, stats: bool = True) -> dict:
+        """dint_log_apply_device: replay n drained records held in HBM (log order) into this engine, `chunk` records per
+        pass (0 = pass_max).  stats=True waits for the replay and returns the acks by kind, the number of chunks and --
+        with timing_enable on -- the nanoseconds per stage; stats=False returns {} once the work is queued."""
+        if not stats:
+            _lib.check(self._L.dint_log_apply_device(self._h, _ptr(d_records), n, chunk, None))
+            return {}
+        s = _lib.ApplyStats()
+        _lib.check(self._L.dint_log_apply_device(self._h, _ptr(d_records), n, chunk, C.byref(s)))
+        d = {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+        d["stage_ns"] = dict(zip(("group", "probe", "apply"), s.reserved))
+        return d
+
     def stats(self) -> dict:
         s = _lib.Stats()
         _lib.check(self._L.dint_get_stats(self._h, C.byref(s)))

@@ -7,12 +7,17 @@ log record becomes the backup operation the client sent right after it (COMMIT_B
 one that does not yet, DELETE_BCK for a DELETE_LOG record), in log order, through the ordinary hot path of the
 replica being rebuilt.  Because COMMIT_BCK bumps the version and INSERT_BCK starts at 0, a replica that starts from
 the same image as the logging server (e.g. the initial population) ends with identical rows AND versions.
+
+Two forms of the same replay.  `apply_log` takes the drained records in host memory and decides in numpy what each
+becomes.  `apply_log_device` / `LogShipper` keep the log in HBM from the primary's ring to the replica's tables
+(dint_log_drain_device, dint_log_apply_device: csrc/k_replay.hip sorts the records of a chunk by row, probes the replica
+once per row and emits the batch on the GPU); primary and replica are engines on the same device, or on peers.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .wire import SB_MSG, TATP_MSG, Sb, Tatp, Workload
+from .wire import LOG_REC, SB_MSG, TATP_MSG, Sb, Tatp, Workload
 
 
 def apply_log(engine, records: np.ndarray) -> dict:
@@ -48,3 +53,37 @@ def apply_log(engine, records: np.ndarray) -> dict:
     rep = engine.submit(m)
     return {"applied": n, "commits": int((rep["type"] == Tatp.COMMIT_BCK_ACK).sum()),
             "inserts": int((rep["type"] == Tatp.INSERT_BCK_ACK).sum()), "deletes": int((rep["type"] == Tatp.DELETE_BCK_ACK).sum())}
+
+
+def apply_log_device(engine, d_records, n: int, chunk: int = 0) -> dict:
+    """apply_log for records that live in HBM (a torch uint8 tensor or a device pointer; n 64-byte records, oldest
+    first, e.g. filled by Engine.log_drain_device): same result, same keys.  `chunk` = records per pass, 0 = pass_max."""
+    if n == 0:
+        return {"applied": 0}
+    st = engine.log_apply_device(d_records, n, chunk)
+    if engine.workload == Workload.SMALLBANK:
+        return {"applied": n, "acks": st["commits"]}
+    return {"applied": n, "commits": st["commits"], "inserts": st["inserts"], "deletes": st["deletes"]}
+
+
+class LogShipper:
+    """Follows a primary's log into a replica: `step()` drains what the primary appended since the last step into one
+    HBM buffer of `cap` records and replays it.  The records never reach host memory (the drain reads the ring's 16-byte
+    tail words, nothing else).  Step at least once per `primary` log ring of appends, or `lost` says what the ring
+    overwrote; a step takes at most `cap` records, the rest waits for the next one."""
+
+    def __init__(self, primary, replica, cap: int = 1 << 20, chunk: int = 0):
+        import torch
+
+        assert primary.workload == replica.workload
+        self.primary, self.replica, self.cap, self.chunk = primary, replica, cap, chunk
+        self.buf = torch.empty(cap * LOG_REC.itemsize, dtype=torch.uint8, device="cuda")
+        self.shipped = self.lost = 0
+
+    def step(self) -> dict:
+        n, lost = self.primary.log_drain_device(self.buf, self.cap)
+        out = apply_log_device(self.replica, self.buf, n, self.chunk)
+        out["lost"] = lost
+        self.shipped += n
+        self.lost += lost
+        return out

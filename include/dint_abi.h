@@ -39,7 +39,8 @@
 extern "C" {
 #endif
 
-#define DINT_ABI_VERSION 4 /* v4 (round 6): dint_submit_device_ahead, dint_stats.late_requests */
+#define DINT_ABI_VERSION 5 /* v4 (round 6): dint_submit_device_ahead, dint_stats.late_requests; v5: dint_log_drain_device,
+                              dint_log_apply_device */
 
 /* dint_config.flags */
 #define DINT_FLAG_KV_ROUNDS 1u /* kv workloads: resolve same-key conflicts request by request instead of in
@@ -260,8 +261,35 @@ int64_t dint_read_log(dint_engine_t *e, void *records, uint64_t cap);
 /* Log drain (the reference writes its logs and never reads them, tatp/udp/server_shard.cc:182-207): copies
  * the records appended since the previous call, oldest first, up to cap; returns how many.  *lost (may be NULL) = records
  * the ring overwrote before they were drained (drain at least once per log_entries appended).  The stream position
- * survives ring wrap-around; dint_reset rewinds it.  dint_amd/recovery.py replays a drained log into a replica. */
+ * survives ring wrap-around; dint_reset rewinds it.  dint_amd/recovery.py replays a drained log into a replica.
+ * dint_log_drain_device / dint_log_apply_device below are the same two steps without the trip through host memory. */
 int64_t dint_log_drain(dint_engine_t *e, void *records, uint64_t cap, uint64_t *lost);
+/* (ABI v5) like dint_log_drain, but the records go to DEVICE memory (64-byte canonical records, oldest first): d_records is
+ * readable and writable from the engine's device.  Shares dint_log_drain's cursor, its `lost` accounting and its contract
+ * (ring wrap, reset / restore) -- the two calls may be mixed.  The copy runs on `stream` (a hipStream_t, NULL = the engine's
+ * own) and is complete when the call returns: like dint_log_drain it synchronises the device to learn the tail; the 16 bytes of
+ * the tail words are all that reaches host memory.  As for dint_log_drain, a batch announced by dint_submit_device_ahead has
+ * its records in the ring already: they are drained with the rest. */
+int64_t dint_log_drain_device(dint_engine_t *e, void *d_records, uint64_t cap, uint64_t *lost, void *stream);
+
+typedef struct dint_apply_stats {
+  uint64_t applied, commits, inserts, deletes; /* records turned into COMMIT_BCK / INSERT_BCK / DELETE_BCK and acked */
+  uint64_t chunks;                             /* passes the stream was cut into */
+  uint64_t reserved[3]; /* diagnostic, with dint_timing_enable on: nanoseconds on the engine's stream spent in [0] the key pass
+                           and the sort, [1] the probe (build, READ pass, classify, emit), [2] the apply pass and the count */
+} dint_apply_stats;
+
+/* (ABI v5) replay n drained records (device pointer, log order) into engine e through its ordinary hot path:
+ * tatp: COMMIT_BCK for a row that exists at that point of the log, INSERT_BCK for one that does not,
+ *       DELETE_BCK for a DELETE_LOG record;  smallbank: COMMIT_BCK, val = the record's first 8 bytes.
+ * chunk = records per pass, 0 = dint_max_pass(e) (larger values are clamped to it).  Everything is enqueued on the engine's
+ * own stream, which must already be ordered behind whatever produced the records (dint_log_drain_device returns with them
+ * complete; dint_stream_wait otherwise).  Returns when the work is queued unless out != NULL, which synchronises the stream
+ * and fills the counts.  The records stay untouched.  Refused before any GPU work: a workload without a KV log target
+ * (DINT_ESTATE), a sharded engine (DINT_EINVAL: routing a log is not done here), a batch announced by
+ * dint_submit_device_ahead still pending (DINT_ESTATE, as dint_snapshot).  The replica's own log is not appended to (backup
+ * operations never are).  Scratch of ~200 bytes per record of a chunk is allocated on the first call and kept. */
+int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t chunk, dint_apply_stats *out);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

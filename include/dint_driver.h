@@ -173,6 +173,13 @@ int dint_lock_gclient_read_batch(dint_lock_gclient_t *c, void *host);
 /* synchronises the device (a consume deferred into the next emit runs now); rollbacks stay 0 for lock_2pl */
 int dint_lock_gclient_get_stats(dint_lock_gclient_t *c, dint_fasst_client_stats *out);
 
+/* ---- log replay: the classification rule on the host (dint_amd/csrc/log_replay.h) --------------------------
+ * What dint_log_apply_device (include/dint_abi.h) decides per record on the GPU, restated on the host for tests and tools:
+ * records = n canonical 64-byte log records in log order; exists0[i] = does record i's row exist before the whole stream
+ * (only read for the first record of a row); types_out[i] = the tatp backup request type dint_amd/recovery.py would
+ * choose (COMMIT_BCK 13 / INSERT_BCK 19 / DELETE_BCK 23).  No device call. */
+int dint_log_classify_host(const void *records, uint64_t n, const uint8_t *exists0, uint8_t *types_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,7 @@ SYMBOLS = [
     "dint_stream_wait", "dint_stream_signal", "dint_route_pack", "dint_route_unpack", "dint_submit_segments",
     "dint_log_drain", "dint_refuse", "dint_route_pack_multi", "dint_route_unpack_multi", "dint_bench_access", "dint_selftest",
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
-    "dint_log_drain_device", "dint_log_apply_device",
+    "dint_log_drain_device", "dint_log_apply_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
 ]
 
 
@@ -59,6 +59,23 @@ class ApplyStats(C.Structure):
     """dint_apply_stats (include/dint_abi.h)"""
     _fields_ = [("applied", C.c_uint64), ("commits", C.c_uint64), ("inserts", C.c_uint64), ("deletes", C.c_uint64),
                 ("chunks", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class TableDigest(C.Structure):
+    """dint_table_digest (include/dint_abi.h)"""
+    _fields_ = [("rows", C.c_uint64), ("sum", C.c_uint64), ("xr", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class DiffStats(C.Structure):
+    """dint_diff_stats (include/dint_abi.h)"""
+    _fields_ = [("total", C.c_uint64), ("only_a", C.c_uint64), ("only_b", C.c_uint64), ("val_differs", C.c_uint64),
+                ("ver_only", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class RepairStats(C.Structure):
+    """dint_repair_stats (include/dint_abi.h)"""
+    _fields_ = [("applied", C.c_uint64), ("updated", C.c_uint64), ("inserted", C.c_uint64), ("deleted", C.c_uint64),
+                ("refused", C.c_uint64), ("reserved", C.c_uint64 * 3)]
 
 
 class DintError(RuntimeError):
@@ -138,8 +155,15 @@ def load() -> C.CDLL:
         "dint_refuse": (C.c_int, [u32, vp, u32, vp]),
         "dint_log_drain_device": (i64, [vp, vp, u64, C.POINTER(u64), vp]),
         "dint_log_apply_device": (C.c_int, [vp, vp, u64, u32, C.POINTER(ApplyStats)]),
+        "dint_state_digest": (C.c_int, [vp, C.POINTER(TableDigest), u32, vp]),
+        "dint_state_diff": (i64, [vp, vp, vp, u64, C.POINTER(DiffStats), vp]),
+        "dint_state_repair": (C.c_int, [vp, vp, u64, C.POINTER(RepairStats), vp]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
+        # ... and the state sync's rules (csrc/state_sync.h) over dumped rows
+        "dint_state_row_hash_host": (u64, [u64, u32, u32, vp, u32]),
+        "dint_state_digest_host": (C.c_int, [u32, vp, vp, vp, u32, u64, C.POINTER(TableDigest)]),
+        "dint_state_diff_host": (i64, [u32, u64, u32, vp, vp, vp, u64, vp, vp, vp, u64, vp, u64, C.POINTER(DiffStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)  # AttributeError here = the .so does not export the ABI

@@ -119,6 +119,32 @@ struct dint_kv_fmt {
 };
 dint_kv_fmt dint_kv_format(uint32_t workload);
 
+// ---- state sync (k_state.hip; state_sync.h): digest / diff / repair of the tables' rows ---------------------------
+struct dint_state_scratch {
+  unsigned long long *words;  // [32] device words: [0..3] the diff's records by kind (state_sync.h SS_*), [4] their number,
+                              // [8] the repair's "records out of order" flag, [9..12] {updated, inserted, deleted, refused},
+                              // [16 ..] the digest: {rows, sum, xor, 0} per table
+  uint32_t *blk_cnt;          // [nb] the diff's records per workgroup of 256 buckets, all tables in table order
+  uint64_t *blk_off;          // [nb] ... their exclusive scan
+  uint32_t nb;                // dint_state_blocks() (0 = blk_cnt / blk_off not allocated)
+  unsigned long long *digest_part;  // [DINT_KV_MAX_TABLES][DINT_STATE_DIGEST_GRID][4] the digest's partial per workgroup
+};
+#define DINT_STATE_DIGEST_GRID 2048u
+#define DINT_STATE_WORDS 48u
+#define DINT_STATE_DIGEST_AT 16u
+uint32_t dint_state_blocks(const dint_kv &kv);
+// {rows, sum, xor, 0} of table t into s.words[DINT_STATE_DIGEST_AT + 4 t ..]
+void dint_launch_state_digest(const dint_kv &kv, dint_state_scratch s, hipStream_t st);
+// what must be done to b's rows to make them a's: the counts into s.words[0..4] and the workgroups' offsets into s.blk_off ...
+void dint_launch_state_diff_count(const dint_kv &a, const dint_kv &b, dint_state_scratch s, hipStream_t st);
+// ... then (same stream, tables untouched in between) the first `cap` records of the contract's order into d_records
+void dint_launch_state_diff_write(const dint_kv &a, const dint_kv &b, dint_state_scratch s, void *d_records, uint64_t cap, hipStream_t st);
+// s.words[8] != 0 afterwards: the n records are not grouped by (table, bucket) in ascending order, or name a table that is not there
+void dint_launch_state_repair_check(const dint_kv &kv, const void *d_records, uint64_t n, dint_state_scratch s, hipStream_t st);
+// applies the records; emptied overflow entries go to pend set `pend_set` (dint_kv_core.h kv_pool_rotate); counts into s.words[9..12]
+void dint_launch_state_repair(const dint_kv &kv, const void *d_records, uint64_t n, uint32_t pend_set, dint_dev_stats *stats,
+                              dint_state_scratch s, hipStream_t st);
+
 // ---- multi-GPU routing (k_route.hip) --------------------------------------------------------------------------
 #define DINT_ROUTE_MAXW 64u        // ranks a batch can be routed to
 #define DINT_ROUTE_MAXN 1048576u   // requests per dint_route_pack call

@@ -129,6 +129,9 @@ struct dint_engine {
   // log replay (dint_log_apply_device): scratch of one chunk, allocated on first use; the events of its stage timing
   dint_replay_scratch replay{};
   hipEvent_t ev_replay[4] = {};
+  // state sync (dint_state_digest / dint_state_diff / dint_state_repair): result words, and -- for the diff, in engine a --
+  // the per-workgroup counts; allocated on first use
+  dint_state_scratch state{};
 
   // kv workloads (store / tatp / smallbank)
   dint_kv kv{};
@@ -528,6 +531,44 @@ int replay_alloc(dint_engine *e, uint32_t cap) {
   return 0;
 }
 
+// state sync scratch: the result words always, the diff's per-workgroup arrays when asked for
+void state_free(dint_engine *e) {
+  hipFree(e->state.words); hipFree(e->state.blk_cnt); hipFree(e->state.blk_off); hipFree(e->state.digest_part);
+  e->state = dint_state_scratch{};
+}
+int state_alloc(dint_engine *e, bool diff) {
+  dint_state_scratch &s = e->state;
+  bool fresh = false;
+  if (!s.words) {
+    if (int rc = dev_alloc((void **)&s.words, DINT_STATE_WORDS * sizeof(unsigned long long))) return rc;
+    fresh = true;
+  }
+  if (!s.digest_part) {
+    if (int rc = dev_alloc((void **)&s.digest_part, (size_t)DINT_KV_MAX_TABLES * DINT_STATE_DIGEST_GRID * 4 * sizeof(unsigned long long), false))
+      return rc;
+  }
+  if (diff && !s.nb) {
+    const uint32_t nb = dint_state_blocks(e->kv);
+    int rc = dev_alloc((void **)&s.blk_cnt, (size_t)nb * sizeof(uint32_t));
+    if (!rc) rc = dev_alloc((void **)&s.blk_off, (size_t)nb * sizeof(uint64_t));
+    if (rc) {
+      hipFree(s.blk_cnt); hipFree(s.blk_off);
+      s.blk_cnt = nullptr; s.blk_off = nullptr;
+      return rc;
+    }
+    s.nb = nb;
+    fresh = true;
+  }
+  if (fresh) HIP_TRY(hipDeviceSynchronize());  // (the zero fills ran on the null stream: the engine's stream does not wait for it)
+  return 0;
+}
+// the checks the three state calls share for one engine, before any GPU work
+int state_check(const dint_engine *e, bool sharded_ok) {
+  if (!e->kv.n_tables) return fail(DINT_ESTATE, "workload has no kv table");
+  if (!sharded_ok && e->shard.count > 1) return fail(DINT_EINVAL, "a sharded engine: rows are not routed here");
+  return 0;
+}
+
 // the records appended since the last drain, oldest first, to host (dint_log_drain) or device memory (dint_log_drain_device):
 // one cursor, one contract
 int64_t log_drain_locked(dint_engine *e, void *records, uint64_t cap, uint64_t *lost, bool to_device, hipStream_t st) {
@@ -761,6 +802,7 @@ void dint_engine_destroy(dint_engine_t *e) {
   if (e->s_d2h && e->s_d2h != e->stream) hipStreamDestroy(e->s_d2h);
   lock_pipe_destroy(e);
   replay_free(e);
+  state_free(e);
   for (hipEvent_t ev : e->ev_replay)
     if (ev) hipEventDestroy(ev);
   hipFree(e->d_lock_tbl);
@@ -1351,6 +1393,110 @@ int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, u
   out->applied = c[0] + c[1] + c[2];
   out->chunks = chunks;
   for (int k = 0; k < 3; k++) out->reserved[k] = (uint64_t)(stage_ms[k] * 1e6);
+  return 0;
+}
+
+int dint_state_digest(dint_engine_t *e, dint_table_digest *out, uint32_t cap_tables, void *stream) {
+  if (!e || !out) return fail(DINT_EINVAL, "null argument");
+  if (int rc = state_check(e, true)) return rc;
+  if (cap_tables < e->kv.n_tables) return fail(DINT_EINVAL, "%u tables, room for %u", e->kv.n_tables, cap_tables);
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = state_alloc(e, false)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  unsigned long long *d = e->state.words + DINT_STATE_DIGEST_AT;
+  dint_launch_state_digest(e->kv, e->state, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = mark_stream(e, st)) return rc;
+  unsigned long long h[DINT_KV_MAX_TABLES * 4];
+  HIP_TRY(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (uint32_t t = 0; t < e->kv.n_tables; t++) {
+    out[t].rows = h[4 * t]; out[t].sum = h[4 * t + 1]; out[t].xr = h[4 * t + 2]; out[t].reserved = 0;
+  }
+  return (int)e->kv.n_tables;
+}
+
+int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uint64_t cap, dint_diff_stats *out, void *stream) {
+  if (!a || !b) return fail(DINT_EINVAL, "null engine");
+  if (a == b) return fail(DINT_EINVAL, "an engine is not compared with itself");
+  if ((cap && !d_records) || ((uintptr_t)d_records & 7)) return fail(DINT_EINVAL, "cap records need an 8-byte aligned buffer");
+  if (!a->kv.n_tables || !b->kv.n_tables) return fail(DINT_ESTATE, "workload has no kv table");
+  if (a->cfg.workload != b->cfg.workload || a->device != b->device) return fail(DINT_EINVAL, "the engines differ in workload or device");
+  for (uint32_t t = 0; t < a->kv.n_tables; t++)
+    if (a->kv.hash_size[t] != b->kv.hash_size[t]) return fail(DINT_EINVAL, "the engines differ in n_rows");
+  if (int rc = state_check(a, false)) return rc;
+  if (int rc = state_check(b, false)) return rc;
+  std::unique_lock<std::mutex> l0(*std::min(&a->mu, &b->mu)), l1(*std::max(&a->mu, &b->mu));  // address order
+  if (a->ahead.valid || b->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  HIP_TRY(hipSetDevice(a->device));
+  if (int rc = state_alloc(a, true)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : a->stream;
+  if (int rc = order_stream(a, st)) return rc;
+  if (int rc = order_stream(b, st)) return rc;
+  dint_launch_state_diff_count(a->kv, b->kv, a->state, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  unsigned long long h[5];
+  HIP_TRY(hipMemcpyAsync(h, a->state.words, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h[4] && d_records && cap) {  // (two engines in sync: one pass over the buckets, nothing to write)
+    dint_launch_state_diff_write(a->kv, b->kv, a->state, d_records, cap, st);
+    err = hipGetLastError();
+    if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  }
+  if (int rc = mark_stream(a, st)) return rc;
+  if (int rc = mark_stream(b, st)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  if (out) {
+    memset(out, 0, sizeof *out);
+    out->total = h[4]; out->only_a = h[0]; out->only_b = h[1]; out->val_differs = h[2]; out->ver_only = h[3];
+  }
+  return (int64_t)std::min<uint64_t>(h[4], d_records ? cap : 0);
+}
+
+int dint_state_repair(dint_engine_t *e, const void *d_records, uint64_t n, dint_repair_stats *out, void *stream) {
+  if (!e || (n && !d_records)) return fail(DINT_EINVAL, "null argument");
+  if (((uintptr_t)d_records & 7) || n > 0x7FFFFFFFull * 256ull) return fail(DINT_EINVAL, "records: 8-byte aligned, fewer than 2^39");
+  if (int rc = state_check(e, false)) return rc;
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (out) memset(out, 0, sizeof *out);
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = state_alloc(e, false)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  dint_launch_state_repair_check(e->kv, d_records, n, e->state, st);
+  unsigned long long h[5];
+  HIP_TRY(hipMemcpyAsync(h, e->state.words + 8, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h[0]) {
+    if (int rc = mark_stream(e, st)) return rc;
+    return fail(DINT_EINVAL, "the records are not grouped by bucket (table and bucket ascending, as dint_state_diff writes them), or name "
+                             "a table the workload has not; nothing was applied");
+  }
+  // An emptied overflow entry goes to the pend set the engine's LAST pass pushed to: the pass after next rotates that set
+  // (dint_kv_core.h kv_pool_rotate), when this kernel is long over -- never the set the next pass's partition is about to rotate.
+  dint_launch_state_repair(e->kv, d_records, n, (uint32_t)(e->scratch.kvs.pass_no & 1), e->scratch.stats, e->state, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = mark_stream(e, st)) return rc;
+  HIP_TRY(hipMemcpyAsync(h, e->state.words + 8, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (out) {
+    out->updated = h[1]; out->inserted = h[2]; out->deleted = h[3]; out->refused = h[4];
+    out->applied = h[1] + h[2] + h[3];
+  }
+  if (h[4]) {
+    // reported here: the host path's own check (dint_wait) must not report these inserts a second time
+    e->pool_seen += h[4];
+    *e->h_pool += h[4];
+    return fail(DINT_ENOMEM, "%llu inserts found the overflow-entry pool full (dint_config.pool_entries); the other records were applied", h[4]);
+  }
   return 0;
 }
 

@@ -206,6 +206,34 @@ class Engine:
         d["stage_ns"] = dict(zip(("group", "probe", "apply"), s.reserved))
         return d
 
+    # ---- state sync (dint_state_digest / dint_state_diff / dint_state_repair) ----------------------------
+    def state_digest(self, stream: int = 0) -> list:
+        """dint_state_digest: per table {rows, sum, xr} over the valid rows -- the row count, and the sum mod 2^64 and the
+        xor of the row hashes (fasthash64 over key | ver | table | val).  Independent of chain layout and bucket order;
+        64 bytes per table reach the host.  A sharded engine digests its local rows."""
+        d = (_lib.TableDigest * 5)()
+        n = _lib.check(self._L.dint_state_digest(self._h, d, 5, stream))
+        return [{"rows": d[t].rows, "sum": d[t].sum, "xr": d[t].xr} for t in range(n)]
+
+    def state_diff(self, other, d_buf=None, cap: int = 0, stream: int = 0):
+        """dint_state_diff: what must be done to `other` to make its visible rows equal this engine's, as 64-byte log
+        records in the HBM buffer d_buf (room for cap records; a torch uint8 tensor or a device pointer; None with cap = 0
+        only counts).  Order: table, bucket, this engine's rows in chain order, then the rows only `other` has.  Returns
+        (records written, stats); stats["total"] is the number the full diff has.  Neither engine is modified."""
+        s = _lib.DiffStats()
+        n = _lib.check(self._L.dint_state_diff(self._h, other._h, None if d_buf is None else _ptr(d_buf), cap, C.byref(s), stream))
+        return n, {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+
+    def state_repair(self, d_records, n: int, stream: int = 0) -> dict:
+        """dint_state_repair: apply n records of state_diff's form and order to this engine with the versions they carry.
+        Raises DintError (DINT_ENOMEM) after applying the rest when inserts found the overflow pool full; `last_repair`
+        holds the counts also then."""
+        s = _lib.RepairStats()
+        rc = self._L.dint_state_repair(self._h, _ptr(d_records), n, C.byref(s), stream)
+        self.last_repair = {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+        _lib.check(rc)
+        return self.last_repair
+
     def stats(self) -> dict:
         s = _lib.Stats()
         _lib.check(self._L.dint_get_stats(self._h, C.byref(s)))

@@ -12,6 +12,10 @@ Two forms of the same replay.  `apply_log` takes the drained records in host mem
 becomes.  `apply_log_device` / `LogShipper` keep the log in HBM from the primary's ring to the replica's tables
 (dint_log_drain_device, dint_log_apply_device: csrc/k_replay.hip sorts the records of a chunk by row, probes the replica
 once per row and emits the batch on the GPU); primary and replica are engines on the same device, or on peers.
+
+A replica that fell behind (the primary's ring lapped the shipper) cannot be caught up from the log.  `resync` compares the
+two engines' tables where they lie (dint_state_diff) and writes the difference into the replica WITH the primary's versions
+(dint_state_repair; csrc/k_state.hip); `Engine.state_digest` says in 64 bytes per table whether two engines hold the same rows.
 """
 from __future__ import annotations
 
@@ -66,24 +70,72 @@ def apply_log_device(engine, d_records, n: int, chunk: int = 0) -> dict:
     return {"applied": n, "commits": st["commits"], "inserts": st["inserts"], "deletes": st["deletes"]}
 
 
+def digests_equal(a, b) -> bool:
+    """do the two engines hold the same rows (keys, versions, values), whatever their chains look like?"""
+    return a.state_digest() == b.state_digest()
+
+
+def resync(primary, replica, cap: int = 1 << 20, max_rounds: int = 8, buf=None) -> dict:
+    """Make the replica's rows equal the primary's without leaving the GPU: rounds of state_diff -> state_repair through one
+    HBM buffer of `cap` records until the diff is empty.  Several rounds when the diff is longer than `cap`, or when the
+    replica holds duplicate rows of a key (the diff sees the visible row only; deleting it uncovers the next).  Returns
+    {rounds: repair calls made, records: records applied, digests_equal}.  What the diff cannot see is not repaired -- a
+    shadowed duplicate of a key that stays visible, on either side -- and digests_equal, the strict check, then says False
+    (as it does when max_rounds did not suffice).  The caller keeps both engines quiet for the
+    duration; both must be unsharded engines of one workload and size on one device."""
+    import torch
+
+    if buf is None:
+        buf = torch.empty(cap * LOG_REC.itemsize, dtype=torch.uint8, device="cuda")
+    rounds = records = 0
+    while True:
+        n, st = primary.state_diff(replica, buf, cap)
+        if st["total"] == 0 or rounds >= max_rounds:
+            break
+        records += replica.state_repair(buf, n)["applied"]
+        rounds += 1
+    return {"rounds": rounds, "records": records, "digests_equal": digests_equal(primary, replica)}
+
+
 class LogShipper:
     """Follows a primary's log into a replica: `step()` drains what the primary appended since the last step into one
     HBM buffer of `cap` records and replays it.  The records never reach host memory (the drain reads the ring's 16-byte
     tail words, nothing else).  Step at least once per `primary` log ring of appends, or `lost` says what the ring
-    overwrote; a step takes at most `cap` records, the rest waits for the next one."""
+    overwrote; a step takes at most `cap` records, the rest waits for the next one.
 
-    def __init__(self, primary, replica, cap: int = 1 << 20, chunk: int = 0):
+    What the ring overwrote cannot be replayed: `resync()` brings the replica back from the primary's tables instead, and
+    with resync_on_loss=True `step()` does so by itself when it finds records lost.  The caller keeps both engines quiet
+    for the duration of a resync (no submissions to either)."""
+
+    def __init__(self, primary, replica, cap: int = 1 << 20, chunk: int = 0, resync_on_loss: bool = False):
         import torch
 
         assert primary.workload == replica.workload
         self.primary, self.replica, self.cap, self.chunk = primary, replica, cap, chunk
         self.buf = torch.empty(cap * LOG_REC.itemsize, dtype=torch.uint8, device="cuda")
-        self.shipped = self.lost = 0
+        self.shipped = self.lost = self.resyncs = 0
+        self.resync_on_loss = resync_on_loss
 
     def step(self) -> dict:
         n, lost = self.primary.log_drain_device(self.buf, self.cap)
+        if lost and self.resync_on_loss:
+            # the drained records are part of what the primary's tables already hold: dropped, not replayed
+            self.lost += lost
+            return {"applied": 0, "lost": lost, "resync": self.resync()}
         out = apply_log_device(self.replica, self.buf, n, self.chunk)
         out["lost"] = lost
         self.shipped += n
         self.lost += lost
+        return out
+
+    def resync(self) -> dict:
+        """Replica := primary, from the tables.  First the primary's drain cursor moves to the tail (a drain whose records
+        are dropped): the records still in the ring are in the primary's rows already, and replayed on top of the repaired
+        replica they would bump versions twice.  Both engines quiet for the duration."""
+        while True:
+            n, _ = self.primary.log_drain_device(self.buf, self.cap)
+            if n == 0:
+                break
+        out = resync(self.primary, self.replica, cap=self.cap, buf=self.buf)
+        self.resyncs += 1
         return out

@@ -290,6 +290,59 @@ typedef struct dint_apply_stats {
  * dint_submit_device_ahead still pending (DINT_ESTATE, as dint_snapshot).  The replica's own log is not appended to (backup
  * operations never are).  Scratch of ~200 bytes per record of a chunk is allocated on the first call and kept. */
 int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t chunk, dint_apply_stats *out);
+/* ---- state sync (v5, additive): is a replica equal to its primary, what differs, and the repair -- on the device ----------
+ * "State" is ROWS ONLY: per table the multiset of valid (key, ver, val) slots.  Lock words, the log ring, the pool's free
+ * lists and the chain layout are per server and transient; a replica rebuilt from a log has other chains than its primary.
+ * The three calls are for store, tatp and smallbank engines (lock / log engines: DINT_ESTATE), are synchronous like
+ * dint_log_drain (they return with their result on the host), order themselves behind the engine's pending work on `stream`
+ * (a hipStream_t, NULL = the engine's own) and refuse an engine with a batch announced by dint_submit_device_ahead still
+ * pending (DINT_ESTATE, as dint_snapshot).  The caller keeps the engines quiet for the duration. */
+typedef struct dint_table_digest {
+  uint64_t rows;     /* valid rows of the table (duplicate keys count once per row) */
+  uint64_t sum, xr;  /* sum mod 2^64 and xor of the row hashes: fasthash64(bytes, len, 0xdeadbeef) over
+                        key (8, LE) | ver (4, LE) | table (1) | 0 0 0 | val (40 or 8) */
+  uint64_t reserved;
+} dint_table_digest;
+/* (v5, additive) out[t] for every table t of the workload (1 / 5 / 2); returns that number (cap_tables smaller: DINT_EINVAL).
+ * Commutative on purpose: the digest depends on neither chain layout nor bucket order.  A sharded engine is accepted: the digest
+ * is of its local rows (rows and sum add up, xr xors, over the shards).  64 bytes per table reach the host. */
+int dint_state_digest(dint_engine_t *e, dint_table_digest *out, uint32_t cap_tables, void *stream);
+
+typedef struct dint_diff_stats {
+  uint64_t total;       /* records the full diff has (also when cap is smaller) = only_a + only_b + val_differs + ver_only */
+  uint64_t only_a;      /* rows of a that b lacks */
+  uint64_t only_b;      /* rows of b that a lacks */
+  uint64_t val_differs; /* rows of both whose values differ (whatever the versions) */
+  uint64_t ver_only;    /* rows of both that differ in the version alone */
+  uint64_t reserved[3];
+} dint_diff_stats;
+/* (v5, additive) what must be done to b to make its rows equal a's, as canonical 64-byte log records (dint_read_log) in
+ * DEVICE memory (8-byte aligned): a row of a that b lacks or holds differently -> {key, a's val zero-padded to 40, a's ver,
+ * is_del = 0, table}; a row only b has -> {key, is_del = 1, table}, val and ver zero; pad zero.  Compared are the VISIBLE rows:
+ * per key the first valid slot in chain order, what a READ returns (a shadowed duplicate is outside the diff; the digest is the
+ * strict check).  The order is fixed: ascending table, ascending bucket; inside a bucket a's rows in a's chain order, then the
+ * b-only rows in b's.  Returns the number of records written (<= cap; the first cap of that order); out (may be NULL) says how
+ * many there are.  d_records == NULL with cap == 0 only counts.  Neither engine is modified.  Refused before any GPU work:
+ * a == b, a null engine, engines of different workloads, table sizes or devices, a sharded engine on either side (DINT_EINVAL);
+ * lock / log engines, an announced batch pending on either (DINT_ESTATE).  Scratch of 12 bytes per 256 buckets is allocated in
+ * a on the first call and kept. */
+int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uint64_t cap, dint_diff_stats *out, void *stream);
+
+typedef struct dint_repair_stats {
+  uint64_t applied;  /* = updated + inserted + deleted */
+  uint64_t updated;  /* the visible row took the record's value and version in place */
+  uint64_t inserted; /* the key was absent: kvs_insert placement, the record's version */
+  uint64_t deleted;  /* kvs_delete of the visible row (a delete of an absent key changes nothing and is counted nowhere) */
+  uint64_t refused;  /* inserts that found the overflow-entry pool full */
+  uint64_t reserved[3];
+} dint_repair_stats;
+/* (v5, additive) applies n records of dint_state_diff's form and ORDER (grouped by bucket: table and bucket ascending) to b WITH THE
+ * VERSIONS THEY CARRY -- a resync, not a log replay (dint_log_apply_device bumps versions as the backup operations do).  The
+ * records of one bucket are applied in order by one lane; buckets run in parallel.  Records out of order, or naming a table the
+ * workload has not: DINT_EINVAL with the tables untouched.  b's lock words, log ring, log cursor and request counters are left
+ * alone.  An insert that finds the pool full is not done: `refused` and dint_stats.pool_exhausted count it, the rest is applied,
+ * the call returns DINT_ENOMEM (as dint_wait).  Same refusals as dint_state_diff for the one engine. */
+int dint_state_repair(dint_engine_t *b, const void *d_records, uint64_t n, dint_repair_stats *out, void *stream);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

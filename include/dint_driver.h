@@ -180,6 +180,23 @@ int dint_lock_gclient_get_stats(dint_lock_gclient_t *c, dint_fasst_client_stats 
  * choose (COMMIT_BCK 13 / INSERT_BCK 19 / DELETE_BCK 23).  No device call. */
 int dint_log_classify_host(const void *records, uint64_t n, const uint8_t *exists0, uint8_t *types_out);
 
+/* ---- state sync: the rules on the host (dint_amd/csrc/state_sync.h) ------------------------------------------
+ * What dint_state_digest / dint_state_diff (include/dint_abi.h) compute on the GPU, restated over dumped rows
+ * (dint_dump_rows: keys, versions, values of val_size = 40 or 8 bytes) for tests and tools.  No device call.
+ * dint_state_row_hash_host: the hash of one row (0 for a null value or another val_size).
+ * dint_state_digest_host: {rows, sum, xr} of n rows of `table`.
+ * dint_state_diff_host: rows a and b of ONE table, each in dump order (bucket order is not needed, chain order inside a
+ * bucket is what the order of equal-bucket rows is taken for), hash_size = dint_hash_size of the table; the records that make
+ * b's visible rows equal a's, in the device call's order; returns how many were written (<= cap), out->total how many there are. */
+struct dint_table_digest; /* include/dint_abi.h */
+struct dint_diff_stats;
+uint64_t dint_state_row_hash_host(uint64_t key, uint32_t ver, uint32_t table, const void *val, uint32_t val_size);
+int dint_state_digest_host(uint32_t table, const uint64_t *keys, const uint32_t *vers, const void *vals, uint32_t val_size,
+                           uint64_t n, struct dint_table_digest *out);
+int64_t dint_state_diff_host(uint32_t table, uint64_t hash_size, uint32_t val_size, const uint64_t *a_keys, const uint32_t *a_vers,
+                             const void *a_vals, uint64_t na, const uint64_t *b_keys, const uint32_t *b_vers, const void *b_vals,
+                             uint64_t nb, void *records, uint64_t cap, struct dint_diff_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

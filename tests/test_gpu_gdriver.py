@@ -13,17 +13,27 @@ pytestmark = pytest.mark.gpu
 W = wire.Workload
 
 
-@pytest.mark.parametrize("wl,n_rows,clients,zipf,epochs,fuse", [
+STREAM_ROWS = [
     (W.TATP, 20_000, 6000, 0.8, 100, 1), (W.TATP, 3000, 5000, None, 100, 1), (W.TATP, 1_000_000, 70_000, 0.8, 40, 1),
     (W.SMALLBANK, 50_000, 4000, 0.99 - 1e-9, 100, 1), (W.SMALLBANK, 600_000, 5000, None, 100, 1),
     (W.TATP, 20_000, 6000, 0.8, 60, 0), (W.SMALLBANK, 50_000, 4000, 0.99 - 1e-9, 60, 0),
-])
-def test_gpu_driver_stream_is_bit_identical_to_the_host_driver(wl, n_rows, clients, zipf, epochs, fuse, monkeypatch):
+]
+# the other two register-budget variants of k_txn_emit (DINT_TXN_WAVES; unset = 4)
+WAVES_ROWS = [(W.TATP, 20_000, 6000, 0.8, 60, 1, 3), (W.SMALLBANK, 50_000, 4000, 0.99 - 1e-9, 60, 1, 3),
+              (W.TATP, 20_000, 6000, 0.8, 60, 0, 5), (W.SMALLBANK, 50_000, 4000, 0.99 - 1e-9, 60, 1, 5)]
+
+
+@pytest.mark.parametrize("wl,n_rows,clients,zipf,epochs,fuse,waves", [r + (None,) for r in STREAM_ROWS] + WAVES_ROWS,
+                         ids=["-".join(map(str, r)) for r in STREAM_ROWS] +
+                             ["-".join(map(str, r[:6])) + f"-waves{r[6]}" for r in WAVES_ROWS])
+def test_gpu_driver_stream_is_bit_identical_to_the_host_driver(wl, n_rows, clients, zipf, epochs, fuse, waves, monkeypatch):
     """fuse = 1: consume on the stream of next() is deferred into the next emit kernel (the batches alternate between
     two buffer sets); fuse = 0 (DINT_TXN_FUSE=0): consume in a kernel of its own"""
     from dint_amd.replay import GpuLoop, ShardGroup
 
     monkeypatch.setenv("DINT_TXN_FUSE", str(fuse))
+    if waves is not None:
+        monkeypatch.setenv("DINT_TXN_WAVES", str(waves))
 
     ga = ShardGroup(wl, n_rows, log_entries=400_000)   # served to the host driver
     gb = ShardGroup(wl, n_rows, log_entries=400_000)   # served to the GPU driver
@@ -54,6 +64,61 @@ def test_gpu_driver_stream_is_bit_identical_to_the_host_driver(wl, n_rows, clien
     for s in range(3):
         for t in range(5 if wl == W.TATP else 2):
             assert all((x == y).all() for x, y in zip(ga.engines[s].dump_rows(t), gb.engines[s].dump_rows(t)))
+
+
+@pytest.mark.parametrize("wl,n_rows,clients,zipf,fuse", [(W.TATP, 20_000, 6000, 0.8, 1), (W.SMALLBANK, 50_000, 4000, None, 0)])
+def test_gpu_driver_full_batch_drops_what_does_not_fit(wl, n_rows, clients, zipf, fuse, monkeypatch):
+    """cap below an epoch's largest batch (the `pos >= cap` branch of k_txn_emit): in the first epoch that overflows,
+    every batch is the host driver's cut at cap, the sizes the engines read are min(size, cap), and `overflow` counts
+    exactly the messages that found no room.  What the clients do after that (each sees its lost request unanswered) is
+    not specified: the loop must go on through real engines without a failing call or a malformed request, and the
+    counters only grow."""
+    from dint_amd.replay import GpuLoop, ShardGroup
+
+    monkeypatch.setenv("DINT_TXN_FUSE", str(fuse))
+    first = Driver(wl, clients, n_rows, first_client=11, zipf_theta=zipf).next()
+    cap = sorted(len(b) for b in first)[1]  # epoch 0: one batch does not fit, one fits exactly, one has room left
+    assert cap >= 2 and max(len(b) for b in first) > cap
+    ga = ShardGroup(wl, n_rows, log_entries=400_000)   # served to the host driver
+    gb = ShardGroup(wl, n_rows, log_entries=400_000)   # served to the GPU driver
+    host = Driver(wl, clients, n_rows, first_client=11, zipf_theta=zipf)
+    gpu = GpuDriver(wl, clients, n_rows, cap, first_client=11, zipf_theta=zipf)
+    loop = GpuLoop(gb, gpu)
+    xs = loop.stream.cuda_stream
+
+    def serve():  # the rest of GpuLoop.epochs(1)
+        for s, eng in enumerate(gb.engines):
+            eng.stream_wait(xs)
+            eng.submit_segments(gpu.batch_ptr[s], 1, cap, cap * gb.msg, gpu.counts_ptr + 4 * s, 0)
+            eng.stream_signal(xs)
+        gpu.consume(xs)
+
+    for e in range(50):
+        want = host.next()
+        gpu.next(xs)
+        loop.stream.synchronize()
+        got = gpu.read_batches()
+        excess = sum(max(len(w) - cap, 0) for w in want)
+        for s in range(3):
+            assert len(got[s]) == min(len(want[s]), cap), (e, s)
+            assert got[s].tobytes() == want[s][:cap].tobytes(), (e, s)
+        assert gpu.stats()["overflow"] == excess
+        serve()
+        if excess:
+            break
+        host.consume(ga.submit(want))
+    assert excess > 0
+    last = gpu.stats()
+    for e in range(20):
+        gpu.next(xs)
+        serve()
+        st = gpu.stats()
+        assert st["messages"] >= last["messages"] and st["overflow"] >= last["overflow"], e
+        last = st
+    loop.sync()
+    assert last["epochs"] > 20 and last["messages"] > 0
+    for eng in gb.engines:
+        assert eng.stats()["bad_requests"] == 0
 
 
 def test_gpu_loop_free_running_matches_oracle_state():

@@ -34,12 +34,21 @@ def _hip():
         L = C.CDLL(path)
         L.hipMemcpyAsync.restype = C.c_int
         L.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.hipMemcpy.restype = C.c_int
+        L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         _HIP = L
     return _HIP
 
 
 def _d2d(dst, src, nbytes, stream):
     assert _hip().hipMemcpyAsync(dst, src, nbytes, 3, stream) == 0  # hipMemcpyDeviceToDevice
+
+
+def _h2d(dst, a):
+    """the bytes of a numpy array to a raw device pointer (blocking)"""
+    a = np.ascontiguousarray(a)
+    if a.nbytes:
+        assert _hip().hipMemcpy(dst, a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
 
 
 def _engine(wl, n_slots):

@@ -27,6 +27,7 @@ SYMBOLS = [
     "dint_log_drain", "dint_refuse", "dint_route_pack_multi", "dint_route_unpack_multi", "dint_bench_access", "dint_selftest",
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
     "dint_log_drain_device", "dint_log_apply_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
+    "dint_state_export", "dint_state_import",
 ]
 
 
@@ -76,6 +77,12 @@ class RepairStats(C.Structure):
     """dint_repair_stats (include/dint_abi.h)"""
     _fields_ = [("applied", C.c_uint64), ("updated", C.c_uint64), ("inserted", C.c_uint64), ("deleted", C.c_uint64),
                 ("refused", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class ImageStats(C.Structure):
+    """dint_image_stats (include/dint_abi.h)"""
+    _fields_ = [("bytes", C.c_uint64), ("buckets", C.c_uint64), ("overflow_entries", C.c_uint64), ("rows", C.c_uint64),
+                ("reserved", C.c_uint64 * 4)]
 
 
 class DintError(RuntimeError):
@@ -158,12 +165,16 @@ def load() -> C.CDLL:
         "dint_state_digest": (C.c_int, [vp, C.POINTER(TableDigest), u32, vp]),
         "dint_state_diff": (i64, [vp, vp, vp, u64, C.POINTER(DiffStats), vp]),
         "dint_state_repair": (C.c_int, [vp, vp, u64, C.POINTER(RepairStats), vp]),
+        "dint_state_export": (C.c_int, [vp, u32, u32, vp, u64, C.POINTER(ImageStats), vp]),
+        "dint_state_import": (C.c_int, [vp, vp, u64, C.POINTER(ImageStats), vp]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
         # ... and the state sync's rules (csrc/state_sync.h) over dumped rows
         "dint_state_row_hash_host": (u64, [u64, u32, u32, vp, u32]),
         "dint_state_digest_host": (C.c_int, [u32, vp, vp, vp, u32, u64, C.POINTER(TableDigest)]),
         "dint_state_diff_host": (i64, [u32, u64, u32, vp, vp, vp, u64, vp, vp, vp, u64, vp, u64, C.POINTER(DiffStats)]),
+        # ... and the state image's check (csrc/state_image.h) over an image in host memory
+        "dint_state_image_check_host": (C.c_int, [vp, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)  # AttributeError here = the .so does not export the ABI

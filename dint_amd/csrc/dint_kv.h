@@ -6,6 +6,7 @@
 
 #include "dint_kernels.h"
 #include "dint_kv_core.h"
+#include "state_image.h"
 
 #define DINT_KV_MAX_TABLES 5
 #define DINT_KV_CTL_BYTES (64 + 24 * KV_NLISTS)  // per table: pool_top, free_head[], pend_head[2][] (two sets: dint_kv_core.h, kv_pool_rotate)
@@ -144,6 +145,34 @@ void dint_launch_state_repair_check(const dint_kv &kv, const void *d_records, ui
 // applies the records; emptied overflow entries go to pend set `pend_set` (dint_kv_core.h kv_pool_rotate); counts into s.words[9..12]
 void dint_launch_state_repair(const dint_kv &kv, const void *d_records, uint64_t n, uint32_t pend_set, dint_dev_stats *stats,
                               dint_state_scratch s, hipStream_t st);
+
+// ---- state image (k_image.hip; state_image.h): the tables written out for another shard layout and read back --------
+struct dint_image_scratch {
+  unsigned long long *words;  // [DINT_IMAGE_WORDS] device words: [2 t] table t's overflow entries, [2 t + 1] its valid slots,
+                              // [DINT_IMAGE_BAD_AT] (u32) export: a chain that does not end / check: the SI_BAD_* found
+  uint2 *blk;                 // [nb] per workgroup of 256 buckets {overflow entries, valid slots}, all tables in table order
+  uint64_t *blk_off;          // [nb] ... the exclusive scan of the entries, per table
+  uint32_t nb;                // workgroups blk / blk_off hold
+  uint2 *inl;                 // [n_inl] export: the image's {head, next} of every selected inline entry
+  uint64_t n_inl;
+  uint32_t *ovf_src;          // [n_ovf] export: the pool index of every overflow entry in image order
+  uint64_t n_ovf;
+};
+#define DINT_IMAGE_WORDS 16u
+#define DINT_IMAGE_BAD_AT 12u
+uint32_t dint_image_blocks(const uint64_t *n, uint32_t n_tables);  // workgroups of 256 for tables of n[t] buckets
+bool dint_image_shape(uint32_t workload, uint32_t *n_tables, uint32_t *stride, uint32_t *val_size);
+// per table the overflow entries and valid slots of the selected buckets into s.words, the workgroups' offsets into s.blk_off ...
+void dint_launch_image_count(const dint_kv &kv, const si_sel *sel, dint_image_scratch s, hipStream_t st);
+// ... then (same stream, tables untouched in between) everything behind the header, laid out as h says
+void dint_launch_image_write(const dint_kv &kv, const si_sel *sel, const si_header &h, dint_image_scratch s, uint8_t *d_buf, hipStream_t st);
+// lock tables: the selected slots to d_slots (nullptr: count only); s.words[1] = the slots with a non-zero word
+void dint_launch_image_lock_out(const uint2 *tbl, si_sel sel, uint8_t *d_slots, dint_image_scratch s, hipStream_t st);
+void dint_launch_image_check(const si_header &h, const uint8_t *d_buf, bool lock, dint_image_scratch s, hipStream_t st);
+// base[t] = the pool entry the image's first overflow entry of table t becomes
+void dint_launch_image_import(const dint_kv &kv, const si_header &h, const uint8_t *d_buf, const uint32_t *base, hipStream_t st);
+void dint_launch_image_lock_in(uint2 *tbl, uint64_t n_local, const si_header &h, const uint8_t *d_buf, hipStream_t st);
+void dint_set_last_error(const char *msg);  // engine.hip: what dint_last_error returns next on this thread
 
 // ---- multi-GPU routing (k_route.hip) --------------------------------------------------------------------------
 #define DINT_ROUTE_MAXW 64u        // ranks a batch can be routed to

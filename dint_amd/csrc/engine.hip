@@ -132,6 +132,11 @@ struct dint_engine {
   // state sync (dint_state_digest / dint_state_diff / dint_state_repair): result words, and -- for the diff, in engine a --
   // the per-workgroup counts; allocated on first use
   dint_state_scratch state{};
+  // state image (dint_state_export / dint_state_import): scratch, grown on demand; `blank` = created or reset and since then
+  // nothing but imports (what dint_state_import asks of its destination); the (source index, source count) pieces imported
+  dint_image_scratch image{};
+  bool blank = true;
+  std::vector<std::pair<uint32_t, uint32_t>> pieces;
 
   // kv workloads (store / tatp / smallbank)
   dint_kv kv{};
@@ -379,6 +384,7 @@ int ahead_cancel(dint_engine *e) {
 int run_pass(dint_engine *e, const void *d_req, uint32_t n, void *d_rep, hipStream_t st, int load_mode = 0,
              const dint_view &view = dint_flat_view(), bool inputs_ready = false, const dint_kv_ahead *next = nullptr) {
   bool part_done = false;
+  e->blank = false;
   if (e->ahead.valid) {  // the pass that was announced, and nothing else
     if (e->ahead.req != d_req || e->ahead.rep != d_rep || e->ahead.n != n || view.seg_cap != e->ahead.seg_cap || load_mode) {
       if (int rc = ahead_cancel(e)) return rc;
@@ -569,6 +575,45 @@ int state_check(const dint_engine *e, bool sharded_ok) {
   return 0;
 }
 
+// state image scratch: every array grows to what a call needs and is kept
+void image_free(dint_engine *e) {
+  hipFree(e->image.words); hipFree(e->image.blk); hipFree(e->image.blk_off); hipFree(e->image.inl); hipFree(e->image.ovf_src);
+  e->image = dint_image_scratch{};
+}
+int image_alloc(dint_engine *e, uint32_t nb, uint64_t n_inl, uint64_t n_ovf) {
+  dint_image_scratch &s = e->image;
+  bool fresh = false;
+  if (!s.words) {
+    if (int rc = dev_alloc((void **)&s.words, DINT_IMAGE_WORDS * sizeof(unsigned long long))) return rc;
+    fresh = true;
+  }
+  if (nb > s.nb || !s.blk) {
+    hipFree(s.blk); hipFree(s.blk_off);
+    s.blk = nullptr; s.blk_off = nullptr; s.nb = 0;
+    int rc = dev_alloc((void **)&s.blk, (size_t)nb * sizeof(uint2));
+    if (!rc) rc = dev_alloc((void **)&s.blk_off, (size_t)nb * sizeof(uint64_t));
+    if (rc) return rc;
+    s.nb = nb;
+    fresh = true;
+  }
+  if (n_inl > s.n_inl) {
+    hipFree(s.inl);
+    s.inl = nullptr; s.n_inl = 0;
+    if (int rc = dev_alloc((void **)&s.inl, (size_t)n_inl * sizeof(uint2), false)) return rc;
+    s.n_inl = n_inl;
+  }
+  if (n_ovf > s.n_ovf) {
+    hipFree(s.ovf_src);
+    s.ovf_src = nullptr; s.n_ovf = 0;
+    if (int rc = dev_alloc((void **)&s.ovf_src, (size_t)n_ovf * sizeof(uint32_t), false)) return rc;
+    s.n_ovf = n_ovf;
+  }
+  if (fresh) HIP_TRY(hipDeviceSynchronize());  // (the zero fills ran on the null stream: the engine's stream does not wait for it)
+  return 0;
+}
+// the layout-relevant flags an image carries
+uint32_t image_flags(const dint_engine *e) { return e->cfg.workload == DINT_WL_TATP ? (e->cfg.flags & DINT_FLAG_LOCK_SAME_KEY) : 0u; }
+
 // the records appended since the last drain, oldest first, to host (dint_log_drain) or device memory (dint_log_drain_device):
 // one cursor, one contract
 int64_t log_drain_locked(dint_engine *e, void *records, uint64_t cap, uint64_t *lost, bool to_device, hipStream_t st) {
@@ -601,6 +646,8 @@ int64_t log_drain_locked(dint_engine *e, void *records, uint64_t cap, uint64_t *
 }
 
 }  // namespace
+
+void dint_set_last_error(const char *msg) { g_err = msg ? msg : ""; }
 
 extern "C" {
 
@@ -803,6 +850,7 @@ void dint_engine_destroy(dint_engine_t *e) {
   lock_pipe_destroy(e);
   replay_free(e);
   state_free(e);
+  image_free(e);
   for (hipEvent_t ev : e->ev_replay)
     if (ev) hipEventDestroy(ev);
   hipFree(e->d_lock_tbl);
@@ -940,6 +988,7 @@ int dint_submit_segments_multi_ahead(const dint_segments_item *items, uint32_t n
   for (uint32_t k = 0; k < n_items; k++) {
     const dint_segments_item &it = items[k];
     dint_engine *e = it.engine;
+    e->blank = false;
     if (int rc = order_stream(e, st)) return rc;
     if (int rc = next_pass_seq(e, st)) return rc;
     pass[k].d_req = it.d_base; pass[k].d_rep = it.d_base; pass[k].n = it.n_seg * it.seg_cap;
@@ -1468,6 +1517,7 @@ int dint_state_repair(dint_engine_t *e, const void *d_records, uint64_t n, dint_
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = state_alloc(e, false)) return rc;
+  e->blank = false;
   hipStream_t st = stream ? (hipStream_t)stream : e->stream;
   if (int rc = order_stream(e, st)) return rc;
   dint_launch_state_repair_check(e->kv, d_records, n, e->state, st);
@@ -1496,6 +1546,169 @@ int dint_state_repair(dint_engine_t *e, const void *d_records, uint64_t n, dint_
     e->pool_seen += h[4];
     *e->h_pool += h[4];
     return fail(DINT_ENOMEM, "%llu inserts found the overflow-entry pool full (dint_config.pool_entries); the other records were applied", h[4]);
+  }
+  return 0;
+}
+
+int dint_state_export(dint_engine_t *e, uint32_t dst_index, uint32_t dst_count, void *d_buf, uint64_t cap_bytes, dint_image_stats *out,
+                      void *stream) {
+  if (!e) return fail(DINT_EINVAL, "null engine");
+  if (dst_count == 0) dst_count = 1;
+  if (dst_index >= dst_count || dst_count > 255) return fail(DINT_EINVAL, "destination shard %u of %u", dst_index, dst_count);
+  if ((uintptr_t)d_buf & 15) return fail(DINT_EINVAL, "an image needs a 16-byte aligned buffer");
+  si_header h;
+  memset(&h, 0, sizeof h);
+  if (!dint_image_shape(e->cfg.workload, &h.n_tables, &h.stride, &h.val_size)) return fail(DINT_ESTATE, "workload has no table");
+  const bool lock = !e->kv.n_tables;
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  HIP_TRY(hipSetDevice(e->device));
+  h.magic = SI_MAGIC; h.version = SI_VERSION; h.workload = e->cfg.workload; h.flags = image_flags(e);
+  h.src_index = e->shard.index; h.src_count = e->shard.count; h.dst_index = dst_index; h.dst_count = dst_count;
+  si_sel sel[SI_MAX_TABLES];
+  uint64_t n_sel[SI_MAX_TABLES] = {0, 0, 0, 0, 0}, n_inl = 0;
+  for (uint32_t t = 0; t < h.n_tables; t++) {
+    h.table[t].global_size = lock ? e->n_slots : e->kv.hash_size[t];
+    sel[t] = si_select(h.table[t].global_size, e->shard.index, e->shard.count, dst_index, dst_count);
+    h.table[t].n_buckets = n_sel[t] = sel[t].n;
+    n_inl += sel[t].n;
+  }
+  if (int rc = image_alloc(e, dint_image_blocks(n_sel, h.n_tables), 0, 0)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  const bool write = d_buf && cap_bytes;
+  unsigned long long w[DINT_IMAGE_WORDS];
+  if (lock) {
+    // (one pass: the size does not depend on the table's contents)
+    h.table[0].offset = SI_HEADER_BYTES;
+    h.bytes = SI_HEADER_BYTES + si_table_bytes(n_sel[0], 0, h.stride, true);
+    if (write && cap_bytes < h.bytes) {
+      if (out) { memset(out, 0, sizeof *out); out->bytes = h.bytes; out->buckets = n_sel[0]; }
+      if (int rc = mark_stream(e, st)) return rc;
+      return fail(DINT_ENOMEM, "the image has %llu bytes, the buffer %llu", (unsigned long long)h.bytes, (unsigned long long)cap_bytes);
+    }
+    dint_launch_image_lock_out(e->d_lock_tbl, sel[0], write ? (uint8_t *)d_buf + SI_HEADER_BYTES : nullptr, e->image, st);
+  } else {
+    dint_launch_image_count(e->kv, sel, e->image, st);
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  HIP_TRY(hipMemcpyAsync(w, e->image.words, sizeof w, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (lock) {
+    h.table[0].rows = w[1];
+  } else {
+    if ((uint32_t)w[DINT_IMAGE_BAD_AT]) {
+      if (int rc = mark_stream(e, st)) return rc;
+      return fail(DINT_ESTATE, "a chain of the source does not end within %u entries, has more than %u overflow entries or leaves the pool: not exported",
+                  KV_MAX_CHAIN, SI_MAX_RUN);
+    }
+    uint64_t at = SI_HEADER_BYTES;
+    for (uint32_t t = 0; t < h.n_tables; t++) {
+      h.table[t].n_overflow = w[2 * t]; h.table[t].rows = w[2 * t + 1]; h.table[t].offset = at;
+      at += si_table_bytes(n_sel[t], h.table[t].n_overflow, h.stride, false);
+    }
+    h.bytes = at;
+  }
+  if (out) {
+    memset(out, 0, sizeof *out);
+    out->bytes = h.bytes;
+    for (uint32_t t = 0; t < h.n_tables; t++) {
+      out->buckets += h.table[t].n_buckets; out->overflow_entries += h.table[t].n_overflow; out->rows += h.table[t].rows;
+    }
+  }
+  if (write && !lock && cap_bytes < h.bytes) {
+    if (int rc = mark_stream(e, st)) return rc;
+    return fail(DINT_ENOMEM, "the image has %llu bytes, the buffer %llu", (unsigned long long)h.bytes, (unsigned long long)cap_bytes);
+  }
+  if (write) {
+    if (!lock) {
+      uint64_t n_ovf = 0;
+      for (uint32_t t = 0; t < h.n_tables; t++) n_ovf += h.table[t].n_overflow;
+      if (int rc = image_alloc(e, 0, n_inl, n_ovf)) return rc;
+      dint_launch_image_write(e->kv, sel, h, e->image, (uint8_t *)d_buf, st);
+      err = hipGetLastError();
+      if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+    }
+    memcpy(e->h_pinned, &h, sizeof h);  // (the page-locked buffer of dint_load_rows: no host submission is in flight under the lock)
+    HIP_TRY(hipMemcpyAsync(d_buf, e->h_pinned, sizeof h, hipMemcpyHostToDevice, st));
+  }
+  if (int rc = mark_stream(e, st)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+int dint_state_import(dint_engine_t *e, const void *d_buf, uint64_t bytes, dint_image_stats *out, void *stream) {
+  if (!e || !d_buf) return fail(DINT_EINVAL, "null argument");
+  if ((uintptr_t)d_buf & 15) return fail(DINT_EINVAL, "an image needs a 16-byte aligned buffer");
+  uint32_t n_tables = 0, stride = 0, val_size = 0;
+  if (!dint_image_shape(e->cfg.workload, &n_tables, &stride, &val_size)) return fail(DINT_ESTATE, "workload has no table");
+  const bool lock = !e->kv.n_tables;
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (!e->blank) return fail(DINT_ESTATE, "the destination is not blank: dint_reset it first (since creation or reset it has taken requests, rows, a log, a repair or a restore)");
+  if (bytes < SI_HEADER_BYTES) return fail(DINT_EINVAL, "image refused: shorter than its header");
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  si_header h;
+  HIP_TRY(hipMemcpyAsync(e->h_pinned, d_buf, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  memcpy(&h, e->h_pinned, sizeof h);
+  // from here on the sizes come from this copy of the header, never from the image again
+  if (h.magic != SI_MAGIC || h.version != SI_VERSION) return fail(DINT_EINVAL, "image refused: not a state image of this version");
+  if (h.workload != e->cfg.workload || h.n_tables != n_tables || h.stride != stride || h.val_size != val_size || h.flags != image_flags(e))
+    return fail(DINT_EINVAL, "image refused: workload %u, flags %u; the engine has workload %u, flags %u", h.workload, h.flags, e->cfg.workload,
+                image_flags(e));
+  if (uint32_t bad = si_header_check(h, bytes, lock)) return fail(DINT_EINVAL, "image refused: %s", si_bad_name(bad));
+  if (h.dst_index != e->shard.index || h.dst_count != e->shard.count)
+    return fail(DINT_EINVAL, "image refused: addressed to shard %u of %u, this is %u of %u", h.dst_index, h.dst_count, e->shard.index, e->shard.count);
+  uint64_t n_b[SI_MAX_TABLES] = {0, 0, 0, 0, 0};
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const uint64_t global = lock ? e->n_slots : e->kv.hash_size[t], n_local = lock ? e->n_local_slots : e->kv.h.tab[t].n_local;
+    if (h.table[t].global_size != global)
+      return fail(DINT_EINVAL, "image refused: table %u has %llu global buckets, the engine's %llu", t, (unsigned long long)h.table[t].global_size,
+                  (unsigned long long)global);
+    if (h.table[t].n_buckets > n_local) return fail(DINT_EINVAL, "image refused: %s", si_bad_name(SI_BAD_SIZE));
+    n_b[t] = h.table[t].n_buckets;
+  }
+  for (const auto &p : e->pieces) {
+    if (p.first == h.src_index && p.second == h.src_count) return fail(DINT_ESTATE, "piece (%u of %u) was imported already", h.src_index, h.src_count);
+    if (p.second != h.src_count) return fail(DINT_ESTATE, "the destination holds pieces of a source of %u shards, this one is of %u", p.second, h.src_count);
+  }
+  uint32_t base[SI_MAX_TABLES] = {0, 0, 0, 0, 0};
+  for (uint32_t t = 0; t < n_tables && !lock; t++) {
+    HIP_TRY(hipMemcpy(&base[t], e->kv.h.tab[t].pool_top, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t cap = e->kv.h.tab[t].pool_cap;
+    if (base[t] > cap) base[t] = cap;
+    if (h.table[t].n_overflow > cap - base[t])
+      return fail(DINT_ENOMEM, "table %u: the image has %llu overflow entries, the pool %u free (dint_config.pool_entries)", t,
+                  (unsigned long long)h.table[t].n_overflow, cap - base[t]);
+  }
+  if (int rc = image_alloc(e, dint_image_blocks(n_b, n_tables), 0, 0)) return rc;
+  dint_launch_image_check(h, (const uint8_t *)d_buf, lock, e->image, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  unsigned long long w[DINT_IMAGE_WORDS];
+  HIP_TRY(hipMemcpyAsync(w, e->image.words, sizeof w, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if ((uint32_t)w[DINT_IMAGE_BAD_AT]) {
+    if (int rc = mark_stream(e, st)) return rc;
+    return fail(DINT_EINVAL, "image refused: %s; no table was touched", si_bad_name((uint32_t)w[DINT_IMAGE_BAD_AT]));
+  }
+  if (lock) dint_launch_image_lock_in(e->d_lock_tbl, e->n_local_slots, h, (const uint8_t *)d_buf, st);
+  else dint_launch_image_import(e->kv, h, (const uint8_t *)d_buf, base, st);
+  err = hipGetLastError();
+  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = mark_stream(e, st)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  e->pieces.push_back({h.src_index, h.src_count});
+  if (out) {
+    memset(out, 0, sizeof *out);
+    out->bytes = bytes;
+    for (uint32_t t = 0; t < n_tables; t++) {
+      out->buckets += h.table[t].n_buckets; out->overflow_entries += h.table[t].n_overflow; out->rows += w[2 * t + 1];
+    }
   }
   return 0;
 }
@@ -1559,6 +1772,8 @@ int dint_reset(dint_engine_t *e) {
   HIP_TRY(hipDeviceSynchronize());
   if (int rc = ahead_cancel(e)) return rc;
   for (auto &r : e->regions) HIP_TRY(hipMemset(r.first, 0, r.second));
+  e->blank = true;
+  e->pieces.clear();
   e->batches = e->requests = 0;
   e->log_drained = 0;
   e->pool_seen = 0;
@@ -1601,6 +1816,7 @@ int dint_restore(dint_engine_t *e) {
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());
   if (int rc = ahead_cancel(e)) return rc;
+  e->blank = false;
   for (size_t i = 0; i < e->regions.size(); i++)
     HIP_TRY(hipMemcpy(e->regions[i].first, e->snap[i], e->regions[i].second, hipMemcpyDeviceToDevice));
   HIP_TRY(hipDeviceSynchronize());

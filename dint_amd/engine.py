@@ -234,6 +234,32 @@ class Engine:
         _lib.check(rc)
         return self.last_repair
 
+    # ---- state image (dint_state_export / dint_state_import) ---------------------------------------------
+    def state_export(self, dst_index: int = 0, dst_count: int = 1, d_buf=None, stream: int = 0):
+        """dint_state_export: the image of everything this engine holds that belongs to shard dst_index of dst_count
+        (csrc/state_image.h: inline entries and chains verbatim, lock words included, links image-relative; lock tables: the
+        slots).  d_buf = an HBM buffer (torch uint8 tensor, 16-byte aligned); None sizes one by a count-only call.  Returns
+        (tensor, nbytes, stats); the engine is left untouched.  Raises DintError (DINT_ENOMEM) when d_buf is too small;
+        `last_image["bytes"]` then says what it takes."""
+        import torch
+
+        s = _lib.ImageStats()
+        if d_buf is None:
+            _lib.check(self._L.dint_state_export(self._h, dst_index, dst_count, None, 0, C.byref(s), stream))
+            d_buf = torch.empty(int(s.bytes), dtype=torch.uint8, device="cuda")
+        rc = self._L.dint_state_export(self._h, dst_index, dst_count, _ptr(d_buf), d_buf.numel(), C.byref(s), stream)
+        self.last_image = {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+        _lib.check(rc)
+        return d_buf, int(s.bytes), self.last_image
+
+    def state_import(self, d_buf, nbytes: int, stream: int = 0) -> dict:
+        """dint_state_import: place an image addressed to this engine's (shard_index, shard_count) into its tables.  The
+        engine must be blank (created or reset, and since then nothing but imports); the image is checked on the device
+        before any table byte changes.  The log ring, the drain cursor and stats() stay as they were."""
+        s = _lib.ImageStats()
+        _lib.check(self._L.dint_state_import(self._h, _ptr(d_buf), nbytes, C.byref(s), stream))
+        return {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+
     def stats(self) -> dict:
         s = _lib.Stats()
         _lib.check(self._L.dint_get_stats(self._h, C.byref(s)))

@@ -16,11 +16,19 @@ once per row and emits the batch on the GPU); primary and replica are engines on
 A replica that fell behind (the primary's ring lapped the shipper) cannot be caught up from the log.  `resync` compares the
 two engines' tables where they lie (dint_state_diff) and writes the difference into the replica WITH the primary's versions
 (dint_state_repair; csrc/k_state.hip); `Engine.state_digest` says in 64 bytes per table whether two engines hold the same rows.
+
+Moving a server to another shard layout is neither: `reshard` carries the tables of a complete set of engines (1 or G
+shards) into a blank set of H shards as state images (dint_state_export / dint_state_import; csrc/k_image.hip) -- entry for
+entry, with lock words, duplicate rows, holes and chain order, so that later replies are those of a set sharded that way from
+the start.  `save_state` / `load_state` put one engine's own image into a file and back.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
+from ._lib import DintError
 from .wire import LOG_REC, SB_MSG, TATP_MSG, Sb, Tatp, Workload
 
 
@@ -95,6 +103,68 @@ def resync(primary, replica, cap: int = 1 << 20, max_rounds: int = 8, buf=None) 
         records += replica.state_repair(buf, n)["applied"]
         rounds += 1
     return {"rounds": rounds, "records": records, "digests_equal": digests_equal(primary, replica)}
+
+
+def image_pieces(G: int, H: int) -> list:
+    """the (i, j) for which the image of source shard i of G for destination shard j of H can hold anything: a global bucket g
+    with g % G == i and g % H == j exists iff i == j mod gcd(G, H)"""
+    G, H = max(1, G), max(1, H)
+    d = math.gcd(G, H)
+    return [(i, j) for i in range(G) for j in range(H) if i % d == j % d]
+
+
+def _image_check_host(image: np.ndarray) -> None:
+    from . import _lib
+
+    image = np.ascontiguousarray(image, np.uint8)
+    _lib.check(_lib.load().dint_state_image_check_host(image.ctypes.data, image.nbytes))
+
+
+def reshard(src_engines, dst_engines, buf=None) -> dict:
+    """Move the tables of `src_engines` (a complete layout: shard i of G at position i) into `dst_engines` (shard j of H at
+    position j), all on one device: every compatible piece (image_pieces) is exported into one HBM buffer and imported from
+    it.  Resets nothing: the destinations must be blank (created or reset, nothing but imports since).  The sources are left
+    untouched; their log rings are not moved (drain them first).  `buf` = a torch uint8 tensor to use (grown when a piece
+    is larger).  Returns the summed stats {bytes, buckets, overflow_entries, rows, pieces}."""
+    G, H = len(src_engines), len(dst_engines)
+    assert all(e.shard_count == G and e.shard_index == i for i, e in enumerate(src_engines)), "sources: a complete layout in index order"
+    assert all(e.shard_count == H and e.shard_index == j for j, e in enumerate(dst_engines)), "destinations: a complete layout in index order"
+    tot = {"bytes": 0, "buckets": 0, "overflow_entries": 0, "rows": 0, "pieces": 0}
+    for i, j in image_pieces(G, H):
+        if buf is None:
+            buf, n, _ = src_engines[i].state_export(j, H)
+        else:
+            try:
+                _, n, _ = src_engines[i].state_export(j, H, buf)
+            except DintError:
+                if src_engines[i].last_image["bytes"] <= buf.numel():
+                    raise
+                buf, n, _ = src_engines[i].state_export(j, H)  # (too small: a buffer of the piece's size from here on)
+        st = dst_engines[j].state_import(buf, n)
+        for k in ("bytes", "buckets", "overflow_entries", "rows"):
+            tot[k] += st[k]
+        tot["pieces"] += 1
+    return tot
+
+
+def save_state(engine, path) -> dict:
+    """The engine's own image -- (i, G) -> (i, G): tables, chains and lock words -- written to a file.  The log ring is NOT
+    part of it (nor are the pool's free lists): drain the log first if its records matter."""
+    buf, n, st = engine.state_export(engine.shard_index, engine.shard_count)
+    buf[:n].cpu().numpy().tofile(path)
+    return st
+
+
+def load_state(engine, path) -> dict:
+    """A file written by save_state into a BLANK engine of the same workload, size, flags and shard.  The file is checked on
+    the host first (dint_state_image_check_host), then uploaded and checked again where it lies.  The log ring is not part
+    of a saved state: the engine's stays as it was."""
+    import torch
+
+    image = np.fromfile(path, np.uint8)
+    _image_check_host(image)
+    buf = torch.from_numpy(image).to("cuda")
+    return engine.state_import(buf, image.nbytes)
 
 
 class LogShipper:

@@ -343,6 +343,38 @@ typedef struct dint_repair_stats {
  * alone.  An insert that finds the pool full is not done: `refused` and dint_stats.pool_exhausted count it, the rest is applied,
  * the call returns DINT_ENOMEM (as dint_wait).  Same refusals as dint_state_diff for the one engine. */
 int dint_state_repair(dint_engine_t *b, const void *d_records, uint64_t n, dint_repair_stats *out, void *stream);
+
+/* ---- state image (v5, additive): an engine's tables moved to another shard layout, cloned or checkpointed -- on the device ----
+ * An IMAGE holds everything of one source engine that belongs to one destination shard, entry for entry: kv workloads -- the
+ * inline entries (whole stride: keys, versions, valid bytes, values, tatp lock bytes, smallbank counters, owner keys) and every
+ * bucket's overflow entries in chain order, links made image-relative, invalid slots and shadowed duplicates where they were;
+ * lock tables -- the slots.  Not in it: the log ring, the pool's free and pend lists, pass scratch.  The byte layout is in
+ * dint_amd/csrc/state_image.h.  An image is plain bytes: any copy carries it to another GPU or a file.  Both calls are
+ * synchronous like dint_state_diff, order themselves behind the engine's pending work on `stream` (NULL = the engine's own) and
+ * refuse a log_server engine and an engine with a batch announced by dint_submit_device_ahead still pending (DINT_ESTATE).
+ * The caller keeps the engine quiet for the duration. */
+typedef struct dint_image_stats {
+  uint64_t bytes;             /* size of the image */
+  uint64_t buckets;           /* kv: buckets; lock tables: slots */
+  uint64_t overflow_entries;  /* chain entries beyond the inline ones */
+  uint64_t rows;              /* valid slots (lock tables: slots with a non-zero word) */
+  uint64_t reserved[4];
+} dint_image_stats;
+/* (v5, additive) the image of every global bucket / slot g that src owns with g % dst_count == dst_index (dst_count 0 or 1:
+ * unsharded) into d_buf (device memory, 16-byte aligned).  src may itself be sharded (i, G): the piece for (j, H) is non-empty
+ * only if i == j mod gcd(G, H); an empty piece is a valid image of zero buckets.  d_buf == NULL or cap_bytes == 0 counts only
+ * and fills out->bytes; a buffer that is too small: DINT_ENOMEM with out->bytes set and nothing written.  src is left untouched. */
+int dint_state_export(dint_engine_t *src, uint32_t dst_index, uint32_t dst_count, void *d_buf, uint64_t cap_bytes, dint_image_stats *out,
+                      void *stream);
+/* (v5, additive) the image's buckets to g / dst_count of dst; its overflow entries become one contiguous range of each table's
+ * pool (one bump of pool_top; free lists are not consulted).  dst must be BLANK: created or dint_reset, and since then nothing
+ * but imports (DINT_ESTATE otherwise); a piece is (source index, source count), importing one twice is DINT_ESTATE.  Refused
+ * before any table byte changes: an image of another workload, flags (DINT_FLAG_LOCK_SAME_KEY), n_rows / n_slots, or addressed
+ * to another (index, count) than dst's (DINT_EINVAL); fewer free pool entries than it needs (DINT_ENOMEM); a malformed image
+ * (DINT_EINVAL: nothing of an image is trusted, a check kernel reads all of it before a table is touched -- sizes against
+ * `bytes`, ids ascending, in range and home to dst, every link 0, 1 or inside its bucket's run of overflow entries, the chain
+ * visiting that run exactly once and in order).  dst's log ring, drain cursor and dint_stats stay as they were. */
+int dint_state_import(dint_engine_t *dst, const void *d_buf, uint64_t bytes, dint_image_stats *out, void *stream);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

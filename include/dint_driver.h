@@ -197,6 +197,16 @@ int64_t dint_state_diff_host(uint32_t table, uint64_t hash_size, uint32_t val_si
                              const void *a_vals, uint64_t na, const uint64_t *b_keys, const uint32_t *b_vers, const void *b_vals,
                              uint64_t nb, void *records, uint64_t cap, struct dint_diff_stats *out);
 
+
+/* ---- state image: the check on the host (dint_amd/csrc/state_image.h) ------------------------------------------------
+ * The rule dint_state_import (include/dint_abi.h) applies on the GPU before it touches a table, over an image of `bytes` bytes
+ * in HOST memory: what a caller runs on a file before uploading it.  Checked: the header against `bytes` and the workload it
+ * names, ids strictly ascending, in range and home to the image's source and destination, every link 0, 1 or inside its
+ * bucket's run of overflow entries, every chain visiting its run exactly once and in order.  (The match with a particular
+ * engine -- n_rows, flags, shard -- is dint_state_import's.)  Returns 0 or DINT_EINVAL; dint_last_error names the first
+ * violation.  No device call. */
+int dint_state_image_check_host(const void *image, uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,7 @@ def test_log_vs_oracle_with_wrap(n, cap):
     ring, t = eng.read_log(cap)
     assert t == o.tail
     assert (np.frombuffer(ring.tobytes(), "u1").reshape(cap, 64) == o.ring).all()
+    assert eng.stats()["bad_requests"] == o.errors
 
 
 # ---------------------------------------------------------------- passes of up to 2^20 requests, hot slots

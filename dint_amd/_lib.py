@@ -27,8 +27,10 @@ SYMBOLS = [
     "dint_log_drain", "dint_refuse", "dint_route_pack_multi", "dint_route_unpack_multi", "dint_bench_access", "dint_selftest",
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
     "dint_log_drain_device", "dint_log_apply_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
-    "dint_state_export", "dint_state_import",
+    "dint_state_export", "dint_state_import", "dint_state_rehash",
 ]
+#: dint_state_rehash flags
+REHASH_DROP_LOCKS = 1
 
 
 class RouteItem(C.Structure):
@@ -83,6 +85,16 @@ class ImageStats(C.Structure):
     """dint_image_stats (include/dint_abi.h)"""
     _fields_ = [("bytes", C.c_uint64), ("buckets", C.c_uint64), ("overflow_entries", C.c_uint64), ("rows", C.c_uint64),
                 ("reserved", C.c_uint64 * 4)]
+
+
+class RehashTableStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("overflow_entries", C.c_uint64), ("longest_chain", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class RehashStats(C.Structure):
+    """dint_rehash_stats (include/dint_abi.h)"""
+    _fields_ = [("rows_seen", C.c_uint64), ("rows_placed", C.c_uint64), ("rows_foreign", C.c_uint64), ("locks_held", C.c_uint64),
+                ("table", RehashTableStats * 5), ("stage_ns", C.c_uint64 * 5), ("reserved", C.c_uint64 * 3)]
 
 
 class DintError(RuntimeError):
@@ -167,6 +179,7 @@ def load() -> C.CDLL:
         "dint_state_repair": (C.c_int, [vp, vp, u64, C.POINTER(RepairStats), vp]),
         "dint_state_export": (C.c_int, [vp, u32, u32, vp, u64, C.POINTER(ImageStats), vp]),
         "dint_state_import": (C.c_int, [vp, vp, u64, C.POINTER(ImageStats), vp]),
+        "dint_state_rehash": (C.c_int, [vp, C.POINTER(vp), u32, u32, C.POINTER(RehashStats), vp]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
         # ... and the state sync's rules (csrc/state_sync.h) over dumped rows
@@ -175,6 +188,8 @@ def load() -> C.CDLL:
         "dint_state_diff_host": (i64, [u32, u64, u32, vp, vp, vp, u64, vp, vp, vp, u64, vp, u64, C.POINTER(DiffStats)]),
         # ... and the state image's check (csrc/state_image.h) over an image in host memory
         "dint_state_image_check_host": (C.c_int, [vp, u64]),
+        # ... and the rehash's layout rule (csrc/state_rehash.h) over keys in source order
+        "dint_state_rehash_place_host": (i64, [vp, u64, u64, u32, u32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)  # AttributeError here = the .so does not export the ABI

@@ -174,6 +174,40 @@ void dint_launch_image_import(const dint_kv &kv, const si_header &h, const uint8
 void dint_launch_image_lock_in(uint2 *tbl, uint64_t n_local, const si_header &h, const uint8_t *d_buf, hipStream_t st);
 void dint_set_last_error(const char *msg);  // engine.hip: what dint_last_error returns next on this thread
 
+// ---- rehash (k_rehash.hip; state_rehash.h): the rows of a set of engines into a blank engine of another bucket count -----------
+struct dint_rehash_scratch {
+  unsigned long long *words;  // [DINT_REHASH_WORDS] device words: per table t at [DINT_REHASH_TABLE_WORDS t ..] {rows of the sources,
+                              // lock words they hold, the plan's scan total = entries << 32 | overflow entries, rows placed, entries
+                              // of the longest chain}; [DINT_REHASH_BAD_AT] (u32) bit 0: a source chain that cannot be walked, bit 1:
+                              // a destination bucket beyond SI_MAX_RUN overflow entries
+  uint2 *blk;                 // [nb] per workgroup of 256 source buckets {rows, lock words}: table by table, inside a table source by source
+  uint64_t *blk_off;          // [nb] ... the exclusive scan of the rows, per table: a workgroup's first row in source order
+  uint32_t nb;
+  uint32_t *key_in, *head;    // [n_max] one table's unsorted keys / run heads
+  uint64_t *loc_in;           // [n_max] ... unsorted locators
+  uint64_t n_max;
+  uint32_t *key_out, *elist;  // [n_all] every table's sorted keys / first rows of its entries, kept for the build
+  uint64_t *loc_out;          // [n_all] ... sorted locators
+  unsigned long long *scan;   // [n_all + tables] ... the scan of state_rehash.h (a table's rows + 1 words)
+  uint64_t n_all;
+  void *tmp;                  // the sort's and the scans' temporary storage
+  size_t tmp_bytes;
+  const uint8_t **src_entries;  // [DINT_KV_MAX_TABLES][SR_MAX_SRCS] the sources' entries[] by table and source number
+};
+#define DINT_REHASH_WORDS 48u
+#define DINT_REHASH_TABLE_WORDS 8u
+#define DINT_REHASH_BAD_AT 40u
+uint32_t dint_rehash_blocks(const dint_kv *const *srcs, uint32_t n_srcs);
+// per table the sources' rows and held lock words into s.words, the workgroups' offsets into s.blk_off ...
+void dint_launch_rehash_count(const dint_kv *const *srcs, uint32_t n_srcs, dint_rehash_scratch s, hipStream_t st);
+int64_t dint_rehash_tmp_bytes(uint64_t n, uint64_t dst_n_local, hipStream_t st);
+// ... then (same stream, tables untouched in between) table t's keys, sort and plan: blk_at = where its workgroups start in s.blk_off
+bool dint_launch_rehash_plan(uint32_t t, const dint_kv *const *srcs, uint32_t n_srcs, uint32_t blk_at, const dint_kv &dst, uint64_t n,
+                             uint64_t row_at, dint_rehash_scratch s, hipStream_t st, hipEvent_t *ev);
+// ... then (the host has compared every table's need with the destination's pool) the destination's entries
+void dint_launch_rehash_build(uint32_t t, const dint_kv &dst, uint64_t n, uint64_t row_at, uint64_t n_ent, uint32_t need,
+                              const uint8_t *const *d_src_entries, dint_rehash_scratch s, hipStream_t st);
+
 // ---- multi-GPU routing (k_route.hip) --------------------------------------------------------------------------
 #define DINT_ROUTE_MAXW 64u        // ranks a batch can be routed to
 #define DINT_ROUTE_MAXN 1048576u   // requests per dint_route_pack call

@@ -16,6 +16,7 @@
 #include "dint_kernels.h"
 #include "dint_kv.h"
 #include "dint_populate.h"
+#include "state_rehash.h"
 
 // k_locks.hip: one half of a lock pass (stage 1 = count + scan / place, 2 = resolve) on `st`
 void dint_launch_lock_stage(uint32_t workload, int stage, const void *d_req, void *d_rep, uint32_t n, uint2 *table, dint_mod slots,
@@ -137,6 +138,9 @@ struct dint_engine {
   dint_image_scratch image{};
   bool blank = true;
   std::vector<std::pair<uint32_t, uint32_t>> pieces;
+  // rehash (dint_state_rehash, in the destination): scratch, grown on demand and kept; the events of its stage timing
+  dint_rehash_scratch rehash{};
+  hipEvent_t ev_rehash[4 + 4 * DINT_KV_MAX_TABLES] = {};
 
   // kv workloads (store / tatp / smallbank)
   dint_kv kv{};
@@ -611,6 +615,59 @@ int image_alloc(dint_engine *e, uint32_t nb, uint64_t n_inl, uint64_t n_ovf) {
   if (fresh) HIP_TRY(hipDeviceSynchronize());  // (the zero fills ran on the null stream: the engine's stream does not wait for it)
   return 0;
 }
+// rehash scratch: every array grows to what a call needs and is kept
+void rehash_free(dint_engine *e) {
+  dint_rehash_scratch &s = e->rehash;
+  hipFree(s.words); hipFree(s.blk); hipFree(s.blk_off); hipFree(s.key_in); hipFree(s.head); hipFree(s.loc_in); hipFree(s.key_out);
+  hipFree(s.elist); hipFree(s.loc_out); hipFree(s.scan); hipFree(s.tmp); hipFree(s.src_entries);
+  s = dint_rehash_scratch{};
+}
+int rehash_alloc(dint_engine *e, uint32_t nb, uint64_t n_max, uint64_t n_all, size_t tmp_bytes) {
+  dint_rehash_scratch &s = e->rehash;
+  bool fresh = false;
+  if (!s.words) {
+    int rc = dev_alloc((void **)&s.words, DINT_REHASH_WORDS * sizeof(unsigned long long));
+    if (!rc) rc = dev_alloc((void **)&s.src_entries, (size_t)DINT_KV_MAX_TABLES * SR_MAX_SRCS * sizeof(uint8_t *));
+    if (rc) return rc;
+    fresh = true;
+  }
+  if (nb > s.nb || !s.blk) {
+    hipFree(s.blk); hipFree(s.blk_off);
+    s.blk = nullptr; s.blk_off = nullptr; s.nb = 0;
+    int rc = dev_alloc((void **)&s.blk, (size_t)nb * sizeof(uint2));
+    if (!rc) rc = dev_alloc((void **)&s.blk_off, (size_t)nb * sizeof(uint64_t));
+    if (rc) return rc;
+    s.nb = nb;
+    fresh = true;
+  }
+  if (n_max > s.n_max) {
+    hipFree(s.key_in); hipFree(s.head); hipFree(s.loc_in);
+    s.key_in = s.head = nullptr; s.loc_in = nullptr; s.n_max = 0;
+    int rc = dev_alloc((void **)&s.key_in, (size_t)n_max * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.head, (size_t)n_max * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.loc_in, (size_t)n_max * sizeof(uint64_t), false);
+    if (rc) return rc;
+    s.n_max = n_max;
+  }
+  if (n_all > s.n_all) {
+    hipFree(s.key_out); hipFree(s.elist); hipFree(s.loc_out); hipFree(s.scan);
+    s.key_out = s.elist = nullptr; s.loc_out = nullptr; s.scan = nullptr; s.n_all = 0;
+    int rc = dev_alloc((void **)&s.key_out, (size_t)n_all * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.elist, (size_t)n_all * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.loc_out, (size_t)n_all * sizeof(uint64_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.scan, (size_t)(n_all + DINT_KV_MAX_TABLES) * sizeof(unsigned long long), false);
+    if (rc) return rc;
+    s.n_all = n_all;
+  }
+  if (tmp_bytes > s.tmp_bytes) {
+    hipFree(s.tmp);
+    s.tmp = nullptr; s.tmp_bytes = 0;
+    if (int rc = dev_alloc(&s.tmp, tmp_bytes, false)) return rc;
+    s.tmp_bytes = tmp_bytes;
+  }
+  if (fresh) HIP_TRY(hipDeviceSynchronize());  // (the zero fills ran on the null stream: the engine's stream does not wait for it)
+  return 0;
+}
 // the layout-relevant flags an image carries
 uint32_t image_flags(const dint_engine *e) { return e->cfg.workload == DINT_WL_TATP ? (e->cfg.flags & DINT_FLAG_LOCK_SAME_KEY) : 0u; }
 
@@ -851,7 +908,10 @@ void dint_engine_destroy(dint_engine_t *e) {
   replay_free(e);
   state_free(e);
   image_free(e);
+  rehash_free(e);
   for (hipEvent_t ev : e->ev_replay)
+    if (ev) hipEventDestroy(ev);
+  for (hipEvent_t ev : e->ev_rehash)
     if (ev) hipEventDestroy(ev);
   hipFree(e->d_lock_tbl);
   hipFree(e->log.ring);
@@ -1709,6 +1769,140 @@ int dint_state_import(dint_engine_t *e, const void *d_buf, uint64_t bytes, dint_
     for (uint32_t t = 0; t < n_tables; t++) {
       out->buckets += h.table[t].n_buckets; out->overflow_entries += h.table[t].n_overflow; out->rows += w[2 * t + 1];
     }
+  }
+  return 0;
+}
+
+int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n_srcs, uint32_t flags, dint_rehash_stats *out, void *stream) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!dst || !srcs) return fail(DINT_EINVAL, "null argument");
+  if (n_srcs == 0 || n_srcs > SR_MAX_SRCS) return fail(DINT_EINVAL, "%u sources: 1 .. %u", n_srcs, SR_MAX_SRCS);
+  if (flags & ~DINT_REHASH_DROP_LOCKS) return fail(DINT_EINVAL, "unknown flags %u", flags);
+  std::vector<dint_engine *> all{dst};
+  for (uint32_t k = 0; k < n_srcs; k++) {
+    dint_engine *s = srcs[k];
+    if (!s) return fail(DINT_EINVAL, "null engine");
+    if (s == dst) return fail(DINT_EINVAL, "the destination is among the sources");
+    if (std::find(all.begin(), all.end(), s) != all.end()) return fail(DINT_EINVAL, "source %u appears twice", k);
+    all.push_back(s);
+  }
+  for (dint_engine *e : all)
+    if (e->cfg.workload != dst->cfg.workload || image_flags(e) != image_flags(dst) || e->device != dst->device)
+      return fail(DINT_EINVAL, "the engines differ in workload, DINT_FLAG_LOCK_SAME_KEY or device");
+  if (!dst->kv.n_tables) return fail(DINT_ESTATE, "workload keeps no keys: nothing to rehash (n_slots cannot be changed this way)");
+  std::sort(all.begin(), all.end());  // address order
+  std::vector<std::unique_lock<std::mutex>> locks;
+  for (dint_engine *e : all) locks.emplace_back(e->mu);
+  for (dint_engine *e : all)
+    if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (!dst->blank || !dst->pieces.empty())
+    return fail(DINT_ESTATE, "the destination is not blank: dint_reset it first (since creation or reset it has taken requests, rows, a log, a repair, a restore or an image)");
+  HIP_TRY(hipSetDevice(dst->device));
+  const uint32_t n_tables = dst->kv.n_tables;
+  std::vector<const dint_kv *> kvs(n_srcs);
+  for (uint32_t k = 0; k < n_srcs; k++) kvs[k] = &srcs[k]->kv;
+  const uint32_t nb = dint_rehash_blocks(kvs.data(), n_srcs);
+  if (int rc = rehash_alloc(dst, nb, 0, 0, 0)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : dst->stream;
+  for (dint_engine *e : all)
+    if (int rc = order_stream(e, st)) return rc;
+  auto done = [&](int rc) {  // every way out after the first enqueue
+    for (dint_engine *e : all)
+      if (int r = mark_stream(e, st)) return r;
+    return rc;
+  };
+  const bool timed = dst->timer.on && out;
+  if (timed)
+    for (hipEvent_t &ev : dst->ev_rehash)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  hipEvent_t *ev = dst->ev_rehash;
+  // 1. count
+  if (timed) HIP_TRY(hipEventRecord(ev[0], st));
+  dint_launch_rehash_count(kvs.data(), n_srcs, dst->rehash, st);
+  if (timed) HIP_TRY(hipEventRecord(ev[1], st));
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return done(fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err)));
+  unsigned long long w[DINT_REHASH_WORDS];
+  HIP_TRY(hipMemcpyAsync(w, dst->rehash.words, sizeof w, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint64_t n_row[DINT_KV_MAX_TABLES] = {0, 0, 0, 0, 0}, n_max = 0, n_all = 0, locks_held = 0;
+  for (uint32_t t = 0; t < n_tables; t++) {
+    n_row[t] = w[DINT_REHASH_TABLE_WORDS * t];
+    locks_held += w[DINT_REHASH_TABLE_WORDS * t + 1];
+    n_max = std::max(n_max, n_row[t]);
+    n_all += n_row[t];
+  }
+  if (out) { out->rows_seen = n_all; out->locks_held = locks_held; }
+  if ((uint32_t)w[DINT_REHASH_BAD_AT] & 1u)
+    return done(fail(DINT_ESTATE, "a chain of a source does not end within %u entries or leaves the pool: nothing was placed", KV_MAX_CHAIN));
+  if (locks_held && !(flags & DINT_REHASH_DROP_LOCKS))
+    return done(fail(DINT_ESTATE, "the sources hold %llu lock words, which cannot follow their keys to another size: release them, or pass "
+                                  "DINT_REHASH_DROP_LOCKS", (unsigned long long)locks_held));
+  if (n_max > SR_MAX_ROWS) return done(fail(DINT_EINVAL, "a table of %llu rows: at most %llu", (unsigned long long)n_max, (unsigned long long)SR_MAX_ROWS));
+  // 2. keys, sort, plan: table by table; what the build needs is kept for every table
+  size_t tmp_bytes = 0;
+  for (uint32_t t = 0; t < n_tables; t++) {
+    if (!n_row[t]) continue;
+    const int64_t b = dint_rehash_tmp_bytes(n_row[t], dst->kv.h.tab[t].n_local, st);
+    if (b < 0) return done(fail(DINT_EHIP, "radix sort: temporary storage query failed"));
+    tmp_bytes = std::max(tmp_bytes, (size_t)b);
+  }
+  if (int rc = rehash_alloc(dst, nb, n_max, n_all, tmp_bytes)) return done(rc);
+  const dint_rehash_scratch &rs = dst->rehash;
+  {
+    std::vector<const uint8_t *> ptrs((size_t)DINT_KV_MAX_TABLES * SR_MAX_SRCS, nullptr);
+    for (uint32_t t = 0; t < n_tables; t++)
+      for (uint32_t k = 0; k < n_srcs; k++) ptrs[(size_t)t * SR_MAX_SRCS + k] = kvs[k]->h.tab[t].entries;
+    HIP_TRY(hipMemcpyAsync(rs.src_entries, ptrs.data(), ptrs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (a pageable source that goes out of scope)
+  }
+  uint64_t row_at[DINT_KV_MAX_TABLES] = {0, 0, 0, 0, 0};
+  uint32_t blk_at = 0;
+  for (uint32_t t = 0; t < n_tables; t++) {
+    row_at[t] = t ? row_at[t - 1] + n_row[t - 1] : 0;
+    if (n_row[t] && !dint_launch_rehash_plan(t, kvs.data(), n_srcs, blk_at, dst->kv, n_row[t], row_at[t], rs, st, timed ? ev + 4 + 4 * t : nullptr))
+      return done(fail(DINT_EHIP, "radix sort or scan failed"));
+    for (uint32_t k = 0; k < n_srcs; k++) blk_at += (uint32_t)((kvs[k]->h.tab[t].n_local + 255) / 256);
+  }
+  err = hipGetLastError();
+  if (err != hipSuccess) return done(fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err)));
+  HIP_TRY(hipMemcpyAsync(w, rs.words, sizeof w, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint64_t n_ent[DINT_KV_MAX_TABLES] = {0, 0, 0, 0, 0}, need[DINT_KV_MAX_TABLES] = {0, 0, 0, 0, 0}, placed = 0;
+  int short_t = -1;
+  for (uint32_t t = 0; t < n_tables; t++) {
+    const unsigned long long *wt = w + DINT_REHASH_TABLE_WORDS * t;
+    n_ent[t] = wt[2] >> 32; need[t] = wt[2] & 0xFFFFFFFFull;
+    placed += wt[3];
+    if (out) { out->table[t].rows = wt[3]; out->table[t].overflow_entries = need[t]; out->table[t].longest_chain = wt[4]; }
+    if (short_t < 0 && need[t] > dst->kv.h.tab[t].pool_cap) short_t = (int)t;
+  }
+  if (out) { out->rows_placed = placed; out->rows_foreign = n_all - placed; }
+  if ((uint32_t)w[DINT_REHASH_BAD_AT] & 2u)
+    return done(fail(DINT_ESTATE, "a bucket of the destination would need more than %u overflow entries: nothing was placed (a larger n_rows)", SI_MAX_RUN));
+  if (short_t >= 0)
+    return done(fail(DINT_ENOMEM, "table %d needs %llu overflow entries, the destination's pool has %u (dint_config.pool_entries); nothing was placed",
+                     short_t, (unsigned long long)need[short_t], dst->kv.h.tab[short_t].pool_cap));
+  // 3. build
+  if (timed) HIP_TRY(hipEventRecord(ev[2], st));
+  for (uint32_t t = 0; t < n_tables; t++)
+    dint_launch_rehash_build(t, dst->kv, n_row[t], row_at[t], n_ent[t], (uint32_t)need[t], rs.src_entries + (size_t)t * SR_MAX_SRCS, rs, st);
+  if (timed) HIP_TRY(hipEventRecord(ev[3], st));
+  dst->blank = false;
+  err = hipGetLastError();
+  if (err != hipSuccess) return done(fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err)));
+  if (int rc = done(0)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  if (timed) {
+    auto ns = [](hipEvent_t a, hipEvent_t b) {
+      float ms = 0;
+      return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (uint64_t)(ms * 1e6) : 0ull;
+    };
+    out->stage_ns[0] = ns(ev[0], ev[1]);
+    for (uint32_t t = 0; t < n_tables; t++)
+      if (n_row[t])
+        for (int k = 0; k < 3; k++) out->stage_ns[1 + k] += ns(ev[4 + 4 * t + k], ev[4 + 4 * t + k + 1]);
+    out->stage_ns[4] = ns(ev[2], ev[3]);
   }
   return 0;
 }

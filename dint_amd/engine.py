@@ -17,6 +17,9 @@ from . import _lib
 from .wire import LOG_REC, MSG_DTYPE, Workload
 
 
+_N_TABLES = {Workload.STORE: 1, Workload.TATP: 5, Workload.SMALLBANK: 2}
+
+
 def _ptr(x):
     """Device pointer of a torch tensor / int."""
     if isinstance(x, int):
@@ -259,6 +262,25 @@ class Engine:
         s = _lib.ImageStats()
         _lib.check(self._L.dint_state_import(self._h, _ptr(d_buf), nbytes, C.byref(s), stream))
         return {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+
+    # ---- rehash (dint_state_rehash) ------------------------------------------------------------------------
+    def state_rehash(self, sources, drop_locks: bool = False, stream: int = 0) -> dict:
+        """dint_state_rehash: fill this BLANK engine with every row of `sources` (engines of the same workload, flags and
+        device, in the order given) whose key is home to it under ITS n_rows and shard (csrc/state_rehash.h: the rows of a
+        bucket in source order, inline entry first, no holes; lock words are not moved).  Returns {rows_seen, rows_placed,
+        rows_foreign, locks_held, tables: [{rows, overflow_entries, longest_chain}], stage_ns}.  Raises DintError on a refusal
+        -- the engine is then untouched and still blank; `last_rehash` holds the stats as far as the call got (locks_held
+        after DINT_ESTATE, the need per table after DINT_ENOMEM)."""
+        sources = list(sources)
+        arr = (C.c_void_p * max(1, len(sources)))(*[e._h for e in sources])
+        s = _lib.RehashStats()
+        rc = self._L.dint_state_rehash(self._h, arr, len(sources), _lib.REHASH_DROP_LOCKS if drop_locks else 0, C.byref(s), stream)
+        d = {k: getattr(s, k) for k in ("rows_seen", "rows_placed", "rows_foreign", "locks_held")}
+        d["tables"] = [{k: getattr(s.table[t], k) for k in ("rows", "overflow_entries", "longest_chain")} for t in range(_N_TABLES.get(self.workload, 0))]
+        d["stage_ns"] = dict(zip(("count", "keys", "sort", "plan", "build"), s.stage_ns))
+        self.last_rehash = d
+        _lib.check(rc)
+        return d
 
     def stats(self) -> dict:
         s = _lib.Stats()

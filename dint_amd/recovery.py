@@ -21,6 +21,11 @@ Moving a server to another shard layout is neither: `reshard` carries the tables
 shards) into a blank set of H shards as state images (dint_state_export / dint_state_import; csrc/k_image.hip) -- entry for
 entry, with lock words, duplicate rows, holes and chain order, so that later replies are those of a set sharded that way from
 the start.  `save_state` / `load_state` put one engine's own image into a file and back.
+
+An image moves buckets whole, so it cannot change the bucket counts fixed when an engine is created.  `rehash` moves ROWS:
+blank engines of another `n_rows` (and, if wanted, another shard count) take the rows of a set of engines where they lie
+(dint_state_rehash; csrc/k_rehash.hip) -- every bucket compact, inline entry first, the rows of a bucket in the order the
+sources held them, so every key's visible row stays its visible row.  Lock words do not move.
 """
 from __future__ import annotations
 
@@ -145,6 +150,50 @@ def reshard(src_engines, dst_engines, buf=None) -> dict:
             tot[k] += st[k]
         tot["pieces"] += 1
     return tot
+
+
+def rehash(src_engines, dst_engines, drop_locks: bool = False) -> dict:
+    """Move the rows of `src_engines` into `dst_engines` -- BLANK engines of the same workload and flags on the same device,
+    with their own n_rows, pool_entries and shard layout: every destination takes all sources (Engine.state_rehash) and keeps
+    the rows that are home to it.  With a complete destination set (shard j of H at position j) every row lands exactly once;
+    this is checked -- the placed rows sum to the sources' rows and the summed digests are equal -- and DintError is raised
+    otherwise.  Sources that hold lock words are refused unless drop_locks (a lock word belongs to a slot of the old size).
+    The sources are only read; their log rings are not moved (drain them first).  Returns {rows_seen, rows_placed,
+    locks_held, tables: per table {rows, overflow_entries, longest_chain} over the destinations, per_engine: [stats]}.
+
+    Growing one server in place::
+
+        big = Engine(Workload.TATP, n_rows=2 * n, pool_entries=..., log_entries=...)   # blank
+        recovery.rehash([server], [big])       # server is quiet meanwhile; a DintError leaves `big` blank and says what it takes
+        server, old = big, server              # swap: later requests go to `big`
+        old.close()
+    """
+    src_engines, dst_engines = list(src_engines), list(dst_engines)
+    per = [d.state_rehash(src_engines, drop_locks=drop_locks) for d in dst_engines]
+    tot = {"rows_seen": per[0]["rows_seen"] if per else 0, "rows_placed": sum(p["rows_placed"] for p in per),
+           "locks_held": per[0]["locks_held"] if per else 0, "per_engine": per, "tables": []}
+    for t in range(len(per[0]["tables"]) if per else 0):
+        tot["tables"].append({"rows": sum(p["tables"][t]["rows"] for p in per),
+                              "overflow_entries": sum(p["tables"][t]["overflow_entries"] for p in per),
+                              "longest_chain": max(p["tables"][t]["longest_chain"] for p in per)})
+    if tot["rows_placed"] != tot["rows_seen"]:
+        raise DintError(f"rehash: the destinations placed {tot['rows_placed']} of the sources' {tot['rows_seen']} rows: not a complete shard set")
+    if digest_sum(src_engines) != digest_sum(dst_engines):
+        raise DintError("rehash: the destinations' digests do not add up to the sources'")
+    return tot
+
+
+def digest_sum(engines) -> list:
+    """the digests of a set of engines added up per table: rows and sum add, xr xors (Engine.state_digest)"""
+    out = None
+    for e in engines:
+        d = e.state_digest()
+        if out is None:
+            out = [dict(x) for x in d]
+        else:
+            for x, y in zip(out, d):
+                x["rows"] += y["rows"]; x["sum"] = (x["sum"] + y["sum"]) % (1 << 64); x["xr"] ^= y["xr"]
+    return out
 
 
 def save_state(engine, path) -> dict:

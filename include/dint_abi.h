@@ -375,6 +375,49 @@ int dint_state_export(dint_engine_t *src, uint32_t dst_index, uint32_t dst_count
  * `bytes`, ids ascending, in range and home to dst, every link 0, 1 or inside its bucket's run of overflow entries, the chain
  * visiting that run exactly once and in order).  dst's log ring, drain cursor and dint_stats stay as they were. */
 int dint_state_import(dint_engine_t *dst, const void *d_buf, uint64_t bytes, dint_image_stats *out, void *stream);
+
+/* ---- rehash (v5, additive): the rows of a set of engines placed into a blank engine of another n_rows -- on the device ----
+ * An image moves buckets whole and so cannot change the bucket counts fixed at dint_engine_create.  A rehash moves ROWS: dst
+ * (store, tatp or smallbank; its own n_rows, shard_index / shard_count and pool_entries) takes every row of srcs[0 .. n_srcs)
+ * whose key is home to it under its own geometry -- g' = fasthash64(key) % dst's hash size of the table, g' % shard_count ==
+ * shard_index, local bucket g' / shard_count.  The sources may be any set, sharded or not; whether they are a complete shard
+ * set is the caller's business.  The layout is fixed (dint_amd/csrc/state_rehash.h): the rows that land in a bucket, taken in
+ * SOURCE ORDER -- position of the engine in srcs, local bucket, chain order, slot: dint_dump_rows order, engine after engine,
+ * shadowed duplicates included -- fill the bucket's inline entry (chain position 0, head = 1) and then overflow entries without
+ * holes; the overflow entries of all buckets are one contiguous range of the pool in bucket order (one bump of pool_top per
+ * table, free lists not consulted).  Key, version and value are copied verbatim, so every key's visible row stays its visible
+ * row and dint_state_digest adds up.  Lock words cannot move (a lock word belongs to hash % (4 hash_size), not to a key): dst's
+ * lock bytes, counters and owner keys are zero, and sources that hold any are refused unless DINT_REHASH_DROP_LOCKS is set.
+ * Synchronous like dint_state_import; orders itself behind every engine's pending work on `stream` (NULL = dst's own); the
+ * caller keeps all engines quiet for the duration.  The sources are only read; dst's log ring, drain cursor and dint_stats
+ * stay as they were.  Every refusal comes before any table byte of dst changes, and dst stays blank:
+ *   DINT_EINVAL  n_srcs == 0 or > 255, dst among srcs, a source twice, engines of different workloads, DINT_FLAG_LOCK_SAME_KEY
+ *                settings or devices, a table of more than 2^32 - 16 rows
+ *   DINT_ESTATE  a lock_fasst / lock_2pl / log engine (no keys; n_slots cannot be changed this way); dst not blank (created or
+ *                dint_reset and nothing since -- an engine that has imported pieces holds rows and is refused too); a batch
+ *                announced by dint_submit_device_ahead pending on any engine; a source chain that does not end within 4096
+ *                entries or leaves the pool; lock words held without DINT_REHASH_DROP_LOCKS (out->locks_held says how many); a
+ *                destination bucket that would need more than 4095 overflow entries
+ *   DINT_ENOMEM  a table needs more overflow entries than dst's pool has: out->table[t].overflow_entries is the need, so the
+ *                caller can create a destination that fits (dint_config.pool_entries)
+ * `out` (may be NULL) is filled as far as the call got, also when it refuses.  After a successful call dst is no longer blank. */
+#define DINT_REHASH_DROP_LOCKS 1u
+typedef struct dint_rehash_stats {
+  uint64_t rows_seen;    /* valid slots of the sources */
+  uint64_t rows_placed;  /* ... of them home to dst */
+  uint64_t rows_foreign; /* ... and home to another shard of dst's layout */
+  uint64_t locks_held;   /* non-zero tatp lock bytes / smallbank counter pairs of the sources (dropped, or the reason of the refusal) */
+  struct {
+    uint64_t rows;             /* rows placed in the table */
+    uint64_t overflow_entries; /* overflow entries they need (pool_top afterwards) */
+    uint64_t longest_chain;    /* entries of the longest chain, the inline entry included */
+    uint64_t reserved;
+  } table[5];
+  uint64_t stage_ns[5]; /* with dint_timing_enable(dst, 1): nanoseconds of count, keys, sort, plan, build between events */
+  uint64_t reserved[3];
+} dint_rehash_stats;
+int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n_srcs, uint32_t flags, dint_rehash_stats *out,
+                      void *stream);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

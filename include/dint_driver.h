@@ -207,6 +207,18 @@ int64_t dint_state_diff_host(uint32_t table, uint64_t hash_size, uint32_t val_si
  * violation.  No device call. */
 int dint_state_image_check_host(const void *image, uint64_t bytes);
 
+/* ---- rehash: the layout rule on the host (dint_amd/csrc/state_rehash.h) -----------------------------------------------
+ * Where dint_state_rehash (include/dint_abi.h) puts the rows of ONE table, restated for tests and tools: keys[0 .. n) = the
+ * keys of the sources' rows in SOURCE ORDER (the sources' dint_dump_rows, concatenated in srcs order), hash_size = the
+ * destination's dint_hash_size of the table, (shard_index, shard_count) = the destination's shard (count 0 or 1: unsharded).
+ * Per row i: bucket_out[i] = the destination's local bucket, or UINT64_MAX for a row that is home to another shard (then
+ * link_out[i] = 0, slot_out[i] = 0); link_out[i] = the entry that holds the row -- 1 = the bucket's inline entry, k >= 2 = pool
+ * entry k - 2 of a destination whose pool was empty; slot_out[i] = 0 .. 3.  Returns the overflow entries the table needs
+ * (pool_top afterwards), or DINT_EINVAL (a null array, hash_size 0, shard_index >= shard_count, n > 2^32 - 16) / DINT_ENOMEM.
+ * No device call. */
+int64_t dint_state_rehash_place_host(const uint64_t *keys, uint64_t n, uint64_t hash_size, uint32_t shard_index, uint32_t shard_count,
+                                     uint64_t *bucket_out, uint32_t *link_out, uint32_t *slot_out);
+
 #ifdef __cplusplus
 }
 #endif

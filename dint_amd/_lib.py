@@ -27,7 +27,7 @@ SYMBOLS = [
     "dint_log_drain", "dint_refuse", "dint_route_pack_multi", "dint_route_unpack_multi", "dint_bench_access", "dint_selftest",
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
     "dint_log_drain_device", "dint_log_apply_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
-    "dint_state_export", "dint_state_import", "dint_state_rehash",
+    "dint_state_export", "dint_state_import", "dint_state_rehash", "dint_state_stats",
 ]
 #: dint_state_rehash flags
 REHASH_DROP_LOCKS = 1
@@ -95,6 +95,17 @@ class RehashStats(C.Structure):
     """dint_rehash_stats (include/dint_abi.h)"""
     _fields_ = [("rows_seen", C.c_uint64), ("rows_placed", C.c_uint64), ("rows_foreign", C.c_uint64), ("locks_held", C.c_uint64),
                 ("table", RehashTableStats * 5), ("stage_ns", C.c_uint64 * 5), ("reserved", C.c_uint64 * 3)]
+
+
+class TableStats(C.Structure):
+    """dint_table_stats (include/dint_abi.h)"""
+    _fields_ = [(k, C.c_uint64) for k in (
+        "buckets", "buckets_empty", "rows", "entries", "overflow_entries", "holes", "inline_first", "inline_unlinked", "hit_entries",
+        "shadowed_rows", "buckets_unchecked", "longest_chain", "longest_chain_bucket", "most_rows", "locks_held", "pool_cap",
+        "pool_top")] + [("chain_hist", C.c_uint64 * 17), ("rows_hist", C.c_uint64 * 33), ("reserved", C.c_uint64 * 13)]
+
+    def as_dict(self) -> dict:
+        return {k: (list(getattr(self, k)) if k.endswith("_hist") else int(getattr(self, k))) for k, _ in self._fields_ if k != "reserved"}
 
 
 class DintError(RuntimeError):
@@ -180,6 +191,7 @@ def load() -> C.CDLL:
         "dint_state_export": (C.c_int, [vp, u32, u32, vp, u64, C.POINTER(ImageStats), vp]),
         "dint_state_import": (C.c_int, [vp, vp, u64, C.POINTER(ImageStats), vp]),
         "dint_state_rehash": (C.c_int, [vp, C.POINTER(vp), u32, u32, C.POINTER(RehashStats), vp]),
+        "dint_state_stats": (C.c_int, [vp, C.POINTER(TableStats), u32, vp]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
         # ... and the state sync's rules (csrc/state_sync.h) over dumped rows
@@ -188,6 +200,8 @@ def load() -> C.CDLL:
         "dint_state_diff_host": (i64, [u32, u64, u32, vp, vp, vp, u64, vp, vp, vp, u64, vp, u64, C.POINTER(DiffStats)]),
         # ... and the state image's check (csrc/state_image.h) over an image in host memory
         "dint_state_image_check_host": (C.c_int, [vp, u64]),
+        # ... and the table report's rule (csrc/state_stats.h) over an image in host memory
+        "dint_state_stats_image_host": (C.c_int, [vp, u64, C.POINTER(TableStats), u32]),
         # ... and the rehash's layout rule (csrc/state_rehash.h) over keys in source order
         "dint_state_rehash_place_host": (i64, [vp, u64, u64, u32, u32, vp, vp, vp]),
     }

@@ -146,6 +146,16 @@ void dint_launch_state_repair_check(const dint_kv &kv, const void *d_records, ui
 void dint_launch_state_repair(const dint_kv &kv, const void *d_records, uint64_t n, uint32_t pend_set, dint_dev_stats *stats,
                               dint_state_scratch s, hipStream_t st);
 
+// ---- table report (k_stats.hip; state_stats.h): occupancy and chain shape, read-only ---------------------------------------
+#define DINT_STATE_STATS_GRID 2048u   // workgroups per table at most (8 per compute unit); they stride over the buckets
+#define DINT_STATE_STATS_WORDS 80u    // = ST_WORDS = sizeof(dint_table_stats) / 8
+struct dint_stats_scratch {
+  unsigned long long *part;  // [DINT_KV_MAX_TABLES][DINT_STATE_STATS_GRID][DINT_STATE_STATS_WORDS] one partial report per workgroup
+  unsigned long long *out;   // [DINT_KV_MAX_TABLES][DINT_STATE_STATS_WORDS] the tables' reports
+};
+// table t's report (state_stats.h words; not yet st_report_finish'ed) into s.out[DINT_STATE_STATS_WORDS t ..]
+void dint_launch_state_stats(const dint_kv &kv, dint_stats_scratch s, hipStream_t st);
+
 // ---- state image (k_image.hip; state_image.h): the tables written out for another shard layout and read back --------
 struct dint_image_scratch {
   unsigned long long *words;  // [DINT_IMAGE_WORDS] device words: [2 t] table t's overflow entries, [2 t + 1] its valid slots,

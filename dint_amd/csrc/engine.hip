@@ -17,6 +17,7 @@
 #include "dint_kv.h"
 #include "dint_populate.h"
 #include "state_rehash.h"
+#include "state_stats.h"
 
 // k_locks.hip: one half of a lock pass (stage 1 = count + scan / place, 2 = resolve) on `st`
 void dint_launch_lock_stage(uint32_t workload, int stage, const void *d_req, void *d_rep, uint32_t n, uint2 *table, dint_mod slots,
@@ -133,6 +134,8 @@ struct dint_engine {
   // state sync (dint_state_digest / dint_state_diff / dint_state_repair): result words, and -- for the diff, in engine a --
   // the per-workgroup counts; allocated on first use
   dint_state_scratch state{};
+  // table report (dint_state_stats): the workgroups' partial reports and the tables' reports, allocated on the first call
+  dint_stats_scratch tstats{};
   // state image (dint_state_export / dint_state_import): scratch, grown on demand; `blank` = created or reset and since then
   // nothing but imports (what dint_state_import asks of its destination); the (source index, source count) pieces imported
   dint_image_scratch image{};
@@ -907,6 +910,8 @@ void dint_engine_destroy(dint_engine_t *e) {
   lock_pipe_destroy(e);
   replay_free(e);
   state_free(e);
+  hipFree(e->tstats.part); hipFree(e->tstats.out);
+  e->tstats = dint_stats_scratch{};
   image_free(e);
   rehash_free(e);
   for (hipEvent_t ev : e->ev_replay)
@@ -1526,6 +1531,41 @@ int dint_state_digest(dint_engine_t *e, dint_table_digest *out, uint32_t cap_tab
   for (uint32_t t = 0; t < e->kv.n_tables; t++) {
     out[t].rows = h[4 * t]; out[t].sum = h[4 * t + 1]; out[t].xr = h[4 * t + 2]; out[t].reserved = 0;
   }
+  return (int)e->kv.n_tables;
+}
+
+int dint_state_stats(dint_engine_t *e, dint_table_stats *out, uint32_t cap_tables, void *stream) {
+  if (!e || !out) return fail(DINT_EINVAL, "null argument");
+  if (int rc = state_check(e, true)) return rc;
+  if (cap_tables < e->kv.n_tables) return fail(DINT_EINVAL, "%u tables, room for %u", e->kv.n_tables, cap_tables);
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  HIP_TRY(hipSetDevice(e->device));
+  dint_stats_scratch &s = e->tstats;
+  if (!s.part) {
+    int rc = dev_alloc((void **)&s.part, (size_t)DINT_KV_MAX_TABLES * DINT_STATE_STATS_GRID * DINT_STATE_STATS_WORDS * sizeof(unsigned long long), false);
+    if (!rc) rc = dev_alloc((void **)&s.out, (size_t)DINT_KV_MAX_TABLES * DINT_STATE_STATS_WORDS * sizeof(unsigned long long), false);
+    if (rc) {
+      hipFree(s.part); hipFree(s.out);
+      s = dint_stats_scratch{};
+      return rc;
+    }
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  dint_launch_state_stats(e->kv, s, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = mark_stream(e, st)) return rc;
+  static_assert(sizeof(dint_table_stats) == DINT_STATE_STATS_WORDS * sizeof(uint64_t), "a report is a dint_table_stats");
+  uint64_t h[DINT_KV_MAX_TABLES][DINT_STATE_STATS_WORDS];
+  HIP_TRY(hipMemcpyAsync(h, s.out, sizeof h, hipMemcpyDeviceToHost, st));  // (the one synchronisation of the call)
+  HIP_TRY(hipStreamSynchronize(st));
+  for (uint32_t t = 0; t < e->kv.n_tables; t++)
+    if (st_report_finish(h[t], e->kv.h.tab[t].pool_cap))
+      return fail(DINT_ESTATE, "a chain of table %u does not end within %u entries, visits its inline entry twice or leaves the pool: no report", t,
+                  KV_MAX_CHAIN);
+  memcpy(out, h, (size_t)e->kv.n_tables * sizeof(dint_table_stats));
   return (int)e->kv.n_tables;
 }
 

@@ -282,6 +282,16 @@ class Engine:
         _lib.check(rc)
         return d
 
+    # ---- table report (dint_state_stats) -------------------------------------------------------------------
+    def state_stats(self, stream: int = 0) -> list:
+        """dint_state_stats: per table a dict of the fields of dint_table_stats (include/dint_abi.h; csrc/state_stats.h is
+        the rule) -- buckets, rows, entries, holes, hit_entries, shadowed_rows, longest_chain, locks_held, the pool words ...,
+        chain_hist and rows_hist as lists.  Every chain is walked once on the device; nothing is modified, and a blank engine
+        stays blank."""
+        s = (_lib.TableStats * 5)()
+        n = _lib.check(self._L.dint_state_stats(self._h, s, 5, stream))
+        return [s[t].as_dict() for t in range(n)]
+
     def stats(self) -> dict:
         s = _lib.Stats()
         _lib.check(self._L.dint_get_stats(self._h, C.byref(s)))

@@ -26,6 +26,10 @@ An image moves buckets whole, so it cannot change the bucket counts fixed when a
 blank engines of another `n_rows` (and, if wanted, another shard count) take the rows of a set of engines where they lie
 (dint_state_rehash; csrc/k_rehash.hip) -- every bucket compact, inline entry first, the rows of a bucket in the order the
 sources held them, so every key's visible row stays its visible row.  Lock words do not move.
+
+WHEN to do that is what `table_stats` / `rehash_advice` answer: the tables' occupancy and chain shape, computed where they lie
+(dint_state_stats; csrc/k_stats.hip), and the small policy on top of it.  `check_tables` lays the chain walk's row count
+beside the digest's flat one.
 """
 from __future__ import annotations
 
@@ -194,6 +198,109 @@ def digest_sum(engines) -> list:
             for x, y in zip(out, d):
                 x["rows"] += y["rows"]; x["sum"] = (x["sum"] + y["sum"]) % (1 << 64); x["xr"] ^= y["xr"]
     return out
+
+
+_SUMMED = ("buckets", "buckets_empty", "rows", "entries", "overflow_entries", "holes", "inline_first", "inline_unlinked", "hit_entries",
+           "shadowed_rows", "buckets_unchecked", "locks_held", "pool_cap", "pool_top")
+NO_BUCKET = (1 << 64) - 1  #: longest_chain_bucket of a table without rows
+
+
+def merge_table_stats(reports) -> list:
+    """per-table reports of several engines (Engine.state_stats) as one: counters and histograms add, longest_chain and most_rows
+    take the maximum, longest_chain_bucket goes with the longest chain (ties: the lowest global id)"""
+    out = None
+    for rep in reports:
+        if out is None:
+            out = [dict(x, chain_hist=list(x["chain_hist"]), rows_hist=list(x["rows_hist"])) for x in rep]
+            continue
+        for x, y in zip(out, rep):
+            for k in _SUMMED:
+                x[k] += y[k]
+            for k in ("chain_hist", "rows_hist"):
+                x[k] = [p + q for p, q in zip(x[k], y[k])]
+            if (y["longest_chain"], -y["longest_chain_bucket"]) > (x["longest_chain"], -x["longest_chain_bucket"]):
+                x["longest_chain"], x["longest_chain_bucket"] = y["longest_chain"], y["longest_chain_bucket"]
+            x["most_rows"] = max(x["most_rows"], y["most_rows"])
+    return out or []
+
+
+def table_stats(engines) -> list:
+    """Engine.state_stats of a sharded set (or any set of engines of one workload) summed per table: see merge_table_stats.
+    pool_cap and pool_top add as well."""
+    return merge_table_stats(e.state_stats() for e in engines)
+
+
+def check_tables(engine) -> dict:
+    """The valid-slot invariant on a live engine: Engine.state_digest is a FLAT scan, right only while a valid byte is set
+    nowhere but in an entry linked into its bucket's chain; Engine.state_stats counts the valid slots a CHAIN WALK reaches.  The
+    two row counts taken back to back: {"ok": equal for every table, "tables": the report per table with "digest_rows" beside
+    "rows"}.  Two existing numbers compared; the engine is quiet meanwhile."""
+    st, dg = engine.state_stats(), engine.state_digest()
+    tables = [dict(s, digest_rows=d["rows"]) for s, d in zip(st, dg)]
+    return {"ok": all(t["rows"] == t["digest_rows"] for t in tables), "tables": tables}
+
+
+def hash_sizes(workload, n_rows: int) -> list:
+    """the global bucket count of every table of an engine created with n_rows: dint_kv_create's formulas (csrc/k_kv.hip),
+    mirrored -- what Engine.hash_size(t) returns.  n_rows = 0 is the reference's own size."""
+    wl = Workload(workload)
+    if wl == Workload.STORE:
+        n = n_rows or 2_000_000
+        hs = [n * 18 // 4]
+    elif wl == Workload.TATP:
+        n = n_rows or 7_000_000
+        hs = [n * 3 // 2 // 4] * 2 + [n * 15 // 4 // 4] * 2 + [n * 45 // 8 // 4]
+    elif wl == Workload.SMALLBANK:
+        n = n_rows or 24_000_000
+        hs = [n * 3 // 2 // 4] * 2
+    else:
+        raise ValueError(f"{wl!r} has no kv table")
+    return [max(1, h) for h in hs]
+
+
+def advise_n_rows(workload, rows, rows_per_bucket=8 / 3) -> int:
+    """the smallest n_rows >= 1 for which every table t has at least rows[t] / rows_per_bucket buckets (hash_sizes)"""
+    from fractions import Fraction
+
+    rpb = Fraction(rows_per_bucket).limit_denominator(1 << 20)
+    need = [math.ceil(Fraction(int(r)) / rpb) for r in rows]
+
+    def fits(n):
+        return all(h >= w for h, w in zip(hash_sizes(workload, n), need))
+
+    hi = 1
+    while not fits(hi):
+        hi *= 2
+    lo = hi // 2  # (lo does not fit, or is 0; the bucket counts never fall as n_rows grows)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if fits(mid) else (mid, hi)
+    return hi
+
+
+def rehash_advice(engines, rows_per_bucket=8 / 3, max_rows_per_bucket=4.0, max_pool_fill=0.5) -> dict:
+    """Is it time to rehash this set of engines (a complete shard set, or one engine), and to which n_rows?  Policy only: one
+    Engine.state_stats per engine, no other device work.
+
+    load of table t = its rows over the set / its GLOBAL bucket count.  `needed` is true when any table's load exceeds
+    max_rows_per_bucket, or any table of any engine has more than max_pool_fill of its overflow pool linked
+    (overflow_entries / pool_cap).  `n_rows` is the smallest value for which every table gets at least rows / rows_per_bucket
+    buckets (advise_n_rows) -- what to create the destinations of `rehash` with, needed or not.  `locks_held` non-zero says
+    `rehash` will need drop_locks=True.  The destination's pool stays with the existing mechanism: a DintError (DINT_ENOMEM)
+    of `rehash` reports the need per table.
+
+    The thresholds are ARGUMENTS, not tuned numbers: 8/3 is the reference's own load (12 rows x 3/2 / 4 slots, the lines
+    dint_kv_create cites), 4.0 the capacity of the inline entry -- beyond it the average bucket overflows -- and 0.5 leaves
+    half the pool for the churn to come.  Returns {needed, n_rows, load: [per table], pool_fill: the largest, locks_held,
+    tables: table_stats}."""
+    engines = list(engines)
+    per = [e.state_stats() for e in engines]
+    tables = merge_table_stats(per)
+    load = [t["rows"] / engines[0].hash_size(k) for k, t in enumerate(tables)]
+    pool_fill = max((t["overflow_entries"] / t["pool_cap"] for rep in per for t in rep if t["pool_cap"]), default=0.0)
+    return {"needed": any(x > max_rows_per_bucket for x in load) or pool_fill > max_pool_fill,
+            "n_rows": advise_n_rows(engines[0].workload, [t["rows"] for t in tables], rows_per_bucket),
+            "load": load, "pool_fill": pool_fill, "locks_held": sum(t["locks_held"] for t in tables), "tables": tables}
 
 
 def save_state(engine, path) -> dict:

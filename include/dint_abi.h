@@ -418,6 +418,40 @@ typedef struct dint_rehash_stats {
 } dint_rehash_stats;
 int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n_srcs, uint32_t flags, dint_rehash_stats *out,
                       void *stream);
+/* ---- table report (v5, additive): occupancy and chain shape of an engine's tables -- read where they lie ----------------
+ * What tells an operator WHEN to rehash: how full the buckets are, how long the chains, how much of the overflow pool is
+ * linked, how many slots are holes or shadowed duplicates, whether lock words are held (dint_state_rehash refuses those).
+ * Every bucket's chain is walked once on the device (dint_amd/csrc/state_stats.h is the rule; header sectors only, values
+ * are never read); about 640 bytes per table reach the host.  Exact, and independent of scheduling. */
+typedef struct dint_table_stats {
+  uint64_t buckets;            /* local buckets */
+  uint64_t buckets_empty;      /* ... without a valid slot */
+  uint64_t rows;               /* valid slots reached by the walk (= dint_table_digest.rows while no valid slot sits outside a chain) */
+  uint64_t entries;            /* entries linked into chains, the inline entry included when it is linked */
+  uint64_t overflow_entries;   /* the pool entries among them */
+  uint64_t holes;              /* 4 * entries - rows */
+  uint64_t inline_first;       /* buckets whose chain starts with the inline entry */
+  uint64_t inline_unlinked;    /* buckets with a non-empty chain that does not contain the inline entry */
+  uint64_t hit_entries;        /* over all valid slots: position of the slot's entry in its chain + 1; / rows = header sectors per lookup of a stored row */
+  uint64_t shadowed_rows;      /* valid slots whose key an earlier valid slot of the bucket holds (chain order): rows - distinct keys */
+  uint64_t buckets_unchecked;  /* buckets of more than 64 entries: walked and counted, but their keys are not compared (nothing in shadowed_rows) */
+  uint64_t longest_chain;      /* entries of the longest chain */
+  uint64_t longest_chain_bucket; /* the lowest global bucket id (local * shard_count + shard_index) that attains it; UINT64_MAX: a table without rows */
+  uint64_t most_rows;          /* valid slots of the fullest bucket */
+  uint64_t locks_held;         /* non-zero tatp lock bytes / smallbank {num_ex, num_sh} pairs with a non-zero word (as dint_rehash_stats.locks_held); store: 0 */
+  uint64_t pool_cap, pool_top; /* the overflow pool: entries it has / handed out so far (pool_top - overflow_entries: reusable or leaked) */
+  uint64_t chain_hist[17];     /* buckets by entries in the chain: 0 .. 15, [16] = 16 or more */
+  uint64_t rows_hist[33];      /* buckets by valid slots: 0 .. 31, [32] = 32 or more */
+  uint64_t reserved[13];
+} dint_table_stats;
+/* (v5, additive) out[t] for every table t of the workload (1 / 5 / 2); returns that number (cap_tables smaller: DINT_EINVAL).
+ * Synchronous like dint_state_digest: orders itself behind the engine's pending work on `stream` (NULL = the engine's own),
+ * one host synchronisation for all tables.  Read-only: tables, lock words, dint_stats, the log ring and the drain cursor stay
+ * as they were, and a blank engine stays blank (it reports zeros and can still be imported or rehashed into).  A sharded engine
+ * reports its local buckets.  Refused: a lock_fasst / lock_2pl / log engine (no keys, no chains), a batch announced by
+ * dint_submit_device_ahead pending (DINT_ESTATE); a chain that does not end within 4096 entries, visits its inline entry twice
+ * or leaves the pool (DINT_ESTATE; dint_last_error names the table).  The caller keeps the engine quiet for the duration. */
+int dint_state_stats(dint_engine_t *e, dint_table_stats *out, uint32_t cap_tables, void *stream);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

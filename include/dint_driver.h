@@ -207,6 +207,18 @@ int64_t dint_state_diff_host(uint32_t table, uint64_t hash_size, uint32_t val_si
  * violation.  No device call. */
 int dint_state_image_check_host(const void *image, uint64_t bytes);
 
+/* ---- table report: the rule on the host (dint_amd/csrc/state_stats.h) ---------------------------------------------------
+ * dint_state_stats (include/dint_abi.h) over a state image of a kv workload in HOST memory: out[t] for every table of the image;
+ * returns that number.  The image first goes through dint_state_image_check_host: a malformed one is refused with DINT_EINVAL
+ * and nothing is walked; cap_tables smaller than the image's tables: DINT_EINVAL; the image of a lock table: DINT_ESTATE.
+ * pool_cap and pool_top are not part of an image and come back 0; longest_chain_bucket is the image's global bucket id.  An
+ * engine's OWN image -- (shard_index, shard_count) exported to that same pair -- holds every bucket with chain order, holes
+ * and lock words intact, so this report over it equals the device's field for field apart from the two pool words (and from
+ * `buckets`, its empty share and histogram bins 0 where a sharded engine's last local bucket lies beyond the table's global
+ * size: an image leaves that bucket out).  No device call. */
+struct dint_table_stats; /* include/dint_abi.h */
+int dint_state_stats_image_host(const void *image, uint64_t bytes, struct dint_table_stats *out, uint32_t cap_tables);
+
 /* ---- rehash: the layout rule on the host (dint_amd/csrc/state_rehash.h) -----------------------------------------------
  * Where dint_state_rehash (include/dint_abi.h) puts the rows of ONE table, restated for tests and tools: keys[0 .. n) = the
  * keys of the sources' rows in SOURCE ORDER (the sources' dint_dump_rows, concatenated in srcs order), hash_size = the

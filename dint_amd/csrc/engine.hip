@@ -581,6 +581,15 @@ int state_check(const dint_engine *e, bool sharded_ok) {
   if (!sharded_ok && e->shard.count > 1) return fail(DINT_EINVAL, "a sharded engine: rows are not routed here");
   return 0;
 }
+// ... under the engine's mutex: the state calls read the tables where they lie, so none runs between an announcement and its pass
+int state_quiet(const dint_engine *e) {
+  return e->ahead.valid ? fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending") : 0;
+}
+// ... after a launcher
+int state_launched() {
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+}
 
 // state image scratch: every array grows to what a call needs and is kept
 void image_free(dint_engine *e) {
@@ -1515,15 +1524,14 @@ int dint_state_digest(dint_engine_t *e, dint_table_digest *out, uint32_t cap_tab
   if (int rc = state_check(e, true)) return rc;
   if (cap_tables < e->kv.n_tables) return fail(DINT_EINVAL, "%u tables, room for %u", e->kv.n_tables, cap_tables);
   std::lock_guard<std::mutex> lk(e->mu);
-  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (int rc = state_quiet(e)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = state_alloc(e, false)) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : e->stream;
   if (int rc = order_stream(e, st)) return rc;
   unsigned long long *d = e->state.words + DINT_STATE_DIGEST_AT;
   dint_launch_state_digest(e->kv, e->state, st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = state_launched()) return rc;
   if (int rc = mark_stream(e, st)) return rc;
   unsigned long long h[DINT_KV_MAX_TABLES * 4];
   HIP_TRY(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st));
@@ -1539,7 +1547,7 @@ int dint_state_stats(dint_engine_t *e, dint_table_stats *out, uint32_t cap_table
   if (int rc = state_check(e, true)) return rc;
   if (cap_tables < e->kv.n_tables) return fail(DINT_EINVAL, "%u tables, room for %u", e->kv.n_tables, cap_tables);
   std::lock_guard<std::mutex> lk(e->mu);
-  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (int rc = state_quiet(e)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   dint_stats_scratch &s = e->tstats;
   if (!s.part) {
@@ -1554,8 +1562,7 @@ int dint_state_stats(dint_engine_t *e, dint_table_stats *out, uint32_t cap_table
   hipStream_t st = stream ? (hipStream_t)stream : e->stream;
   if (int rc = order_stream(e, st)) return rc;
   dint_launch_state_stats(e->kv, s, st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = state_launched()) return rc;
   if (int rc = mark_stream(e, st)) return rc;
   static_assert(sizeof(dint_table_stats) == DINT_STATE_STATS_WORDS * sizeof(uint64_t), "a report is a dint_table_stats");
   uint64_t h[DINT_KV_MAX_TABLES][DINT_STATE_STATS_WORDS];
@@ -1580,22 +1587,21 @@ int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uin
   if (int rc = state_check(a, false)) return rc;
   if (int rc = state_check(b, false)) return rc;
   std::unique_lock<std::mutex> l0(*std::min(&a->mu, &b->mu)), l1(*std::max(&a->mu, &b->mu));  // address order
-  if (a->ahead.valid || b->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (int rc = state_quiet(a)) return rc;
+  if (int rc = state_quiet(b)) return rc;
   HIP_TRY(hipSetDevice(a->device));
   if (int rc = state_alloc(a, true)) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : a->stream;
   if (int rc = order_stream(a, st)) return rc;
   if (int rc = order_stream(b, st)) return rc;
   dint_launch_state_diff_count(a->kv, b->kv, a->state, st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = state_launched()) return rc;
   unsigned long long h[5];
   HIP_TRY(hipMemcpyAsync(h, a->state.words, sizeof h, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (h[4] && d_records && cap) {  // (two engines in sync: one pass over the buckets, nothing to write)
     dint_launch_state_diff_write(a->kv, b->kv, a->state, d_records, cap, st);
-    err = hipGetLastError();
-    if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+    if (int rc = state_launched()) return rc;
   }
   if (int rc = mark_stream(a, st)) return rc;
   if (int rc = mark_stream(b, st)) return rc;
@@ -1612,7 +1618,7 @@ int dint_state_repair(dint_engine_t *e, const void *d_records, uint64_t n, dint_
   if (((uintptr_t)d_records & 7) || n > 0x7FFFFFFFull * 256ull) return fail(DINT_EINVAL, "records: 8-byte aligned, fewer than 2^39");
   if (int rc = state_check(e, false)) return rc;
   std::lock_guard<std::mutex> lk(e->mu);
-  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (int rc = state_quiet(e)) return rc;
   if (out) memset(out, 0, sizeof *out);
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(e->device));
@@ -1632,8 +1638,7 @@ int dint_state_repair(dint_engine_t *e, const void *d_records, uint64_t n, dint_
   // An emptied overflow entry goes to the pend set the engine's LAST pass pushed to: the pass after next rotates that set
   // (dint_kv_core.h kv_pool_rotate), when this kernel is long over -- never the set the next pass's partition is about to rotate.
   dint_launch_state_repair(e->kv, d_records, n, (uint32_t)(e->scratch.kvs.pass_no & 1), e->scratch.stats, e->state, st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = state_launched()) return rc;
   if (int rc = mark_stream(e, st)) return rc;
   HIP_TRY(hipMemcpyAsync(h, e->state.words + 8, sizeof h, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1661,7 +1666,7 @@ int dint_state_export(dint_engine_t *e, uint32_t dst_index, uint32_t dst_count, 
   if (!dint_image_shape(e->cfg.workload, &h.n_tables, &h.stride, &h.val_size)) return fail(DINT_ESTATE, "workload has no table");
   const bool lock = !e->kv.n_tables;
   std::lock_guard<std::mutex> lk(e->mu);
-  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (int rc = state_quiet(e)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   h.magic = SI_MAGIC; h.version = SI_VERSION; h.workload = e->cfg.workload; h.flags = image_flags(e);
   h.src_index = e->shard.index; h.src_count = e->shard.count; h.dst_index = dst_index; h.dst_count = dst_count;
@@ -1691,8 +1696,7 @@ int dint_state_export(dint_engine_t *e, uint32_t dst_index, uint32_t dst_count, 
   } else {
     dint_launch_image_count(e->kv, sel, e->image, st);
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = state_launched()) return rc;
   HIP_TRY(hipMemcpyAsync(w, e->image.words, sizeof w, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (lock) {
@@ -1727,8 +1731,7 @@ int dint_state_export(dint_engine_t *e, uint32_t dst_index, uint32_t dst_count, 
       for (uint32_t t = 0; t < h.n_tables; t++) n_ovf += h.table[t].n_overflow;
       if (int rc = image_alloc(e, 0, n_inl, n_ovf)) return rc;
       dint_launch_image_write(e->kv, sel, h, e->image, (uint8_t *)d_buf, st);
-      err = hipGetLastError();
-      if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+      if (int rc = state_launched()) return rc;
     }
     memcpy(e->h_pinned, &h, sizeof h);  // (the page-locked buffer of dint_load_rows: no host submission is in flight under the lock)
     HIP_TRY(hipMemcpyAsync(d_buf, e->h_pinned, sizeof h, hipMemcpyHostToDevice, st));
@@ -1745,7 +1748,7 @@ int dint_state_import(dint_engine_t *e, const void *d_buf, uint64_t bytes, dint_
   if (!dint_image_shape(e->cfg.workload, &n_tables, &stride, &val_size)) return fail(DINT_ESTATE, "workload has no table");
   const bool lock = !e->kv.n_tables;
   std::lock_guard<std::mutex> lk(e->mu);
-  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  if (int rc = state_quiet(e)) return rc;
   if (!e->blank) return fail(DINT_ESTATE, "the destination is not blank: dint_reset it first (since creation or reset it has taken requests, rows, a log, a repair or a restore)");
   if (bytes < SI_HEADER_BYTES) return fail(DINT_EINVAL, "image refused: shorter than its header");
   HIP_TRY(hipSetDevice(e->device));
@@ -1787,8 +1790,7 @@ int dint_state_import(dint_engine_t *e, const void *d_buf, uint64_t bytes, dint_
   }
   if (int rc = image_alloc(e, dint_image_blocks(n_b, n_tables), 0, 0)) return rc;
   dint_launch_image_check(h, (const uint8_t *)d_buf, lock, e->image, st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = state_launched()) return rc;
   unsigned long long w[DINT_IMAGE_WORDS];
   HIP_TRY(hipMemcpyAsync(w, e->image.words, sizeof w, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1798,8 +1800,7 @@ int dint_state_import(dint_engine_t *e, const void *d_buf, uint64_t bytes, dint_
   }
   if (lock) dint_launch_image_lock_in(e->d_lock_tbl, e->n_local_slots, h, (const uint8_t *)d_buf, st);
   else dint_launch_image_import(e->kv, h, (const uint8_t *)d_buf, base, st);
-  err = hipGetLastError();
-  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (int rc = state_launched()) return rc;
   if (int rc = mark_stream(e, st)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   e->pieces.push_back({h.src_index, h.src_count});
@@ -1834,7 +1835,7 @@ int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n
   std::vector<std::unique_lock<std::mutex>> locks;
   for (dint_engine *e : all) locks.emplace_back(e->mu);
   for (dint_engine *e : all)
-    if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+    if (int rc = state_quiet(e)) return rc;
   if (!dst->blank || !dst->pieces.empty())
     return fail(DINT_ESTATE, "the destination is not blank: dint_reset it first (since creation or reset it has taken requests, rows, a log, a repair, a restore or an image)");
   HIP_TRY(hipSetDevice(dst->device));
@@ -1860,8 +1861,7 @@ int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n
   if (timed) HIP_TRY(hipEventRecord(ev[0], st));
   dint_launch_rehash_count(kvs.data(), n_srcs, dst->rehash, st);
   if (timed) HIP_TRY(hipEventRecord(ev[1], st));
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return done(fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err)));
+  if (int rc = state_launched()) return done(rc);
   unsigned long long w[DINT_REHASH_WORDS];
   HIP_TRY(hipMemcpyAsync(w, dst->rehash.words, sizeof w, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1904,8 +1904,7 @@ int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n
       return done(fail(DINT_EHIP, "radix sort or scan failed"));
     for (uint32_t k = 0; k < n_srcs; k++) blk_at += (uint32_t)((kvs[k]->h.tab[t].n_local + 255) / 256);
   }
-  err = hipGetLastError();
-  if (err != hipSuccess) return done(fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err)));
+  if (int rc = state_launched()) return done(rc);
   HIP_TRY(hipMemcpyAsync(w, rs.words, sizeof w, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   uint64_t n_ent[DINT_KV_MAX_TABLES] = {0, 0, 0, 0, 0}, need[DINT_KV_MAX_TABLES] = {0, 0, 0, 0, 0}, placed = 0;
@@ -1929,8 +1928,7 @@ int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n
     dint_launch_rehash_build(t, dst->kv, n_row[t], row_at[t], n_ent[t], (uint32_t)need[t], rs.src_entries + (size_t)t * SR_MAX_SRCS, rs, st);
   if (timed) HIP_TRY(hipEventRecord(ev[3], st));
   dst->blank = false;
-  err = hipGetLastError();
-  if (err != hipSuccess) return done(fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err)));
+  if (int rc = state_launched()) return done(rc);
   if (int rc = done(0)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   if (timed) {

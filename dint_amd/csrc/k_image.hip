@@ -5,7 +5,7 @@
 //   k_image_count      one lane per SELECTED bucket (local bucket l0 + k * step of the source: state_image.h si_select): the
 //                      overflow entries and valid slots of its chain.  Reads the 16-byte link vector of the inline header;
 //                      head 0, or head 1 with no successor -> no walk.  Per workgroup one {entries, slots} pair.
-//   k_image_scan       exclusive scan of the workgroups' entry counts of one table, and the two totals
+//   k_state_scan       (state_dev.h) exclusive scan of the workgroups' entry counts of one table, and the two totals
 //   k_image_dir        (the host has read the totals and knows the image's size by now)  the count again, a scan inside the
 //                      workgroup: the bucket's directory record {global bucket, first, count} goes to the image, its two
 //                      rewritten link words and -- buckets with overflow entries walk a second time -- the pool index of
@@ -18,7 +18,8 @@
 //   k_image_copy_in    the stream back: bucket g to local bucket g / H, overflow entry x to pool entry base + x, links >= 2
 //                      moved by base; one workgroup's first lane sets pool_top.  No atomics: every entry has one lane group.
 //   k_image_lock_out / k_image_lock_in   lock tables: {global slot, a, b} per selected slot
-// Every chain walk counts to KV_MAX_CHAIN and checks its links against the pool's size (export) or the bucket's run (check).
+// Every chain walk is state_image.h si_chain_walk: to KV_MAX_CHAIN entries, every link checked against the pool's size (export:
+// state_dev.h sd_bucket) or the bucket's run (check: si_image_chain) before it is followed.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -30,120 +31,50 @@
 #include "../../include/dint_driver.h"
 #include "dint_kernels.h"
 #include "dint_kv.h"
+#include "state_dev.h"
 #include "state_image.h"
 
-#define SI_TB 256u     // threads per workgroup, every kernel here
+#define SI_TB SD_TB    // threads per workgroup, every kernel here
 #define SI_UNROLL 4u   // copy kernels: entries per lane group (vectors in flight per lane)
 
-typedef uint32_t si_v4 __attribute__((ext_vector_type(4)));
-typedef uint32_t si_v2 __attribute__((ext_vector_type(2)));
-
-__device__ static inline uint32_t si_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-// q = h / f.d (dint_device.h dint_fastmod's quotient)
-__device__ static inline uint64_t si_div(uint64_t h, dint_mod f) {
-  if (f.d <= 1) return h;
-  uint64_t q = __umul64hi(h, f.m);
-  if (h - q * f.d >= f.d) q++;
-  return q;
-}
-
 // ------------------------------------------------------------------------------------------------------ export
-// the chain of local bucket b as it lies in the source's table
-struct si_src_chain {
-  kv_tab t;
-  uint64_t b;
-  __device__ inline bool link_ok(uint32_t link) const { return link - 2u < t.pool_cap; }
-  __device__ inline void load(uint32_t link, uint32_t &validw, uint32_t &next) const {
-    const si_v2 v = *(const KV_G(si_v2) *)(kv_entry_ptr(t, b, link) + KV_VALID_OFF);
-    validw = v.x;
-    next = v.y;
-  }
-};
-// lv = {validw, next, head, lockw} of the inline entry
-template <class F>
-__device__ static inline si_walk si_src_walk(const kv_tab &t, uint64_t b, si_v4 &lv, F &&on_ovf) {
-  lv = *((const KV_G(si_v4) *)kv_entry_ptr(t, b, KV_INLINE) + SI_LINK_VEC);
-  if (lv.z == KV_NULL) return si_walk{0, 0, 0, 0, 1};
-  if (lv.z == KV_INLINE && lv.y == KV_NULL) return si_walk{0, 0, si_valid_count(lv.x), 1, 1};
-  const si_src_chain ch = {t, b};
-  return si_walk_chain(lv.z, ch, on_ovf);
-}
-
 // blk[workgroup] = {overflow entries, valid slots} of its 256 selected buckets; *badw |= 1: a chain that does not end, or has
 // more overflow entries than the check accepts (SI_MAX_RUN): an engine never exports an image its own import refuses
-__global__ void __launch_bounds__(SI_TB) k_image_count(kv_tab t, si_sel s, si_v2 *__restrict__ blk, uint32_t *badw) {
+__global__ void __launch_bounds__(SI_TB) k_image_count(kv_tab t, si_sel s, sd_v2 *__restrict__ blk, uint32_t *badw) {
   __shared__ uint32_t red[SI_TB / 64][2];
   const uint64_t k = (uint64_t)blockIdx.x * SI_TB + threadIdx.x;
   uint32_t c = 0, r = 0;
   if (k < s.n) {
-    si_v4 lv;
-    const si_walk w = si_src_walk(t, s.l0 + k * s.step, lv, [](uint32_t, uint32_t) { return true; });
+    const si_walk w = sd_bucket_walk(sd_bucket_at(t, s.l0 + k * s.step), [](uint32_t, uint32_t) { return true; });
     c = w.count;
     r = w.rows;
     if (!w.ok || w.count > SI_MAX_RUN) atomicOr(badw, 1u);
   }
-  c = si_wave_sum(c);
-  r = si_wave_sum(r);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = c; red[threadIdx.x >> 6][1] = r; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    si_v2 o = {0, 0};
-    for (uint32_t w = 0; w < SI_TB / 64; w++) { o.x += red[w][0]; o.y += red[w][1]; }
-    blk[blockIdx.x] = o;
-  }
-}
-
-// off[i] = blk[0].x + .. + blk[i - 1].x; total[0] = the sum of the .x, total[1] = the sum of the .y.  One workgroup of 1,024.
-__global__ void __launch_bounds__(1024) k_image_scan(const si_v2 *__restrict__ blk, uint32_t nb, uint64_t *__restrict__ off,
-                                                     unsigned long long *total) {
-  __shared__ uint64_t part[1024], party[1024];
-  const uint32_t t = threadIdx.x, per = (nb + 1023u) / 1024u;
-  const uint32_t lo = min(nb, t * per), hi = min(nb, lo + per);
-  uint64_t s = 0, sy = 0;
-  for (uint32_t i = lo; i < hi; i++) { s += blk[i].x; sy += blk[i].y; }
-  part[t] = s;
-  party[t] = sy;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {  // inclusive scan of the threads' sums
-    const uint64_t y = t >= d ? part[t - d] : 0, yy = t >= d ? party[t - d] : 0;
-    __syncthreads();
-    part[t] += y;
-    party[t] += yy;
-    __syncthreads();
-  }
-  uint64_t run = part[t] - s;
-  for (uint32_t i = lo; i < hi; i++) {
-    off[i] = run;
-    run += blk[i].x;
-  }
-  if (t == 1023) { total[0] = part[1023]; total[1] = party[1023]; }
+  sd_block_sum(red, {c, r});
+  if (threadIdx.x == 0) blk[blockIdx.x] = sd_v2{sd_block_total(red, 0), sd_block_total(red, 1)};
 }
 
 // dir[k] = bucket k's directory record; inl[k] = {head, next} of its inline entry as the image has them; ovf_src[x] = the pool
 // index of what becomes overflow entry x (n_ovf of them: nothing is stored beyond, whatever the tables say by now)
-__global__ void __launch_bounds__(SI_TB) k_image_dir(kv_tab t, si_sel s, const uint64_t *__restrict__ blk_off, si_v4 *__restrict__ dir,
-                                                     si_v2 *__restrict__ inl, uint32_t *__restrict__ ovf_src, uint64_t n_ovf) {
+__global__ void __launch_bounds__(SI_TB) k_image_dir(kv_tab t, si_sel s, const uint64_t *__restrict__ blk_off, sd_v4 *__restrict__ dir,
+                                                     sd_v2 *__restrict__ inl, uint32_t *__restrict__ ovf_src, uint64_t n_ovf) {
   __shared__ uint32_t red[SI_TB / 64];
   const uint64_t k = (uint64_t)blockIdx.x * SI_TB + threadIdx.x;
   const uint64_t b = s.l0 + k * s.step;
-  si_v4 lv = {0, 0, 0, 0};
+  sd_v4 lv = {0, 0, 0, 0};
   si_walk w = {0, 0, 0, 0, 1};
-  if (k < s.n) w = si_src_walk(t, b, lv, [](uint32_t, uint32_t) { return true; });
-  uint32_t tot;
-  uint32_t before = wave_excl_scan_u32(w.count, &tot);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tot;
-  __syncthreads();
-  for (uint32_t v = 0; v < (threadIdx.x >> 6); v++) before += red[v];
+  if (k < s.n) {
+    const sd_bucket ch = sd_bucket_at(t, b);
+    lv = ch.lv;
+    w = sd_bucket_walk(ch, [](uint32_t, uint32_t) { return true; });
+  }
+  const uint32_t before = sd_block_excl_scan(red, w.count);
   if (k >= s.n) return;
   const uint64_t first = blk_off[blockIdx.x] + before, g = b * s.G + s.i;
-  dir[k] = si_v4{(uint32_t)g, (uint32_t)(g >> 32), (uint32_t)first, w.count};
-  inl[k] = si_v2{si_head_out(lv.z, first), si_inline_next_out(lv.y, w.linked != 0, first, w.before)};
+  dir[k] = sd_v4{(uint32_t)g, (uint32_t)(g >> 32), (uint32_t)first, w.count};
+  inl[k] = sd_v2{si_head_out(lv.z, first), si_inline_next_out(lv.y, w.linked != 0, first, w.before)};
   if (w.count)
-    si_src_walk(t, b, lv, [=](uint32_t m, uint32_t link) {
+    sd_bucket_walk(sd_bucket_at(t, b), [=](uint32_t m, uint32_t link) {
       if (first + m < n_ovf) ovf_src[first + m] = link - 2u;
       return true;
     });
@@ -151,13 +82,13 @@ __global__ void __launch_bounds__(SI_TB) k_image_dir(kv_tab t, si_sel s, const u
 
 // entries [0, s.n) = the selected inline entries, [s.n, s.n + n_ovf) = the overflow entries in image order
 template <uint32_t STRIDE>
-__global__ void __launch_bounds__(SI_TB) k_image_copy_out(kv_tab t, si_sel s, uint64_t n_ovf, const si_v2 *__restrict__ inl,
+__global__ void __launch_bounds__(SI_TB) k_image_copy_out(kv_tab t, si_sel s, uint64_t n_ovf, const sd_v2 *__restrict__ inl,
                                                           const uint32_t *__restrict__ ovf_src, uint8_t *img_inl, uint8_t *img_ovf) {
   constexpr uint32_t VPE = STRIDE / 16, EPS = SI_TB / VPE;  // vectors per entry, entries per step of the workgroup
   const uint32_t v = threadIdx.x % VPE;
   const uint64_t e0 = (uint64_t)blockIdx.x * (EPS * SI_UNROLL) + threadIdx.x / VPE, n = s.n + n_ovf;
-  si_v4 x[SI_UNROLL];
-  si_v2 l[SI_UNROLL];
+  sd_v4 x[SI_UNROLL];
+  sd_v2 l[SI_UNROLL];
 #pragma unroll
   for (uint32_t u = 0; u < SI_UNROLL; u++) {
     const uint64_t e = e0 + u * EPS;
@@ -170,7 +101,7 @@ __global__ void __launch_bounds__(SI_TB) k_image_copy_out(kv_tab t, si_sel s, ui
       const uint32_t p = ovf_src[e - s.n];
       at = t.n_local + (p < t.pool_cap ? p : 0u);
     }
-    x[u] = __builtin_nontemporal_load((const KV_G(si_v4) *)(t.entries + at * STRIDE) + v);
+    x[u] = __builtin_nontemporal_load((const KV_G(sd_v4) *)(t.entries + at * STRIDE) + v);
   }
 #pragma unroll
   for (uint32_t u = 0; u < SI_UNROLL; u++) {
@@ -181,30 +112,24 @@ __global__ void __launch_bounds__(SI_TB) k_image_copy_out(kv_tab t, si_sel s, ui
       else x[u].y = si_next_out(x[u].y, e - s.n);
     }
     uint8_t *dst = e < s.n ? img_inl + e * STRIDE : img_ovf + (e - s.n) * STRIDE;
-    __builtin_nontemporal_store(x[u], (KV_G(si_v4) *)dst + v);
+    __builtin_nontemporal_store(x[u], (KV_G(sd_v4) *)dst + v);
   }
 }
 
 // lock tables: out == nullptr only counts.  blk[workgroup] = {0, slots with a non-zero word}
-__global__ void __launch_bounds__(SI_TB) k_image_lock_out(const uint2 *__restrict__ tbl, si_sel s, si_v4 *__restrict__ out,
-                                                          si_v2 *__restrict__ blk) {
-  __shared__ uint32_t red[SI_TB / 64];
+__global__ void __launch_bounds__(SI_TB) k_image_lock_out(const uint2 *__restrict__ tbl, si_sel s, sd_v4 *__restrict__ out,
+                                                          sd_v2 *__restrict__ blk) {
+  __shared__ uint32_t red[SI_TB / 64][1];
   const uint64_t k = (uint64_t)blockIdx.x * SI_TB + threadIdx.x;
   uint32_t r = 0;
   if (k < s.n) {
     const uint64_t l = s.l0 + k * s.step, g = l * s.G + s.i;
-    const si_v2 w = *((const KV_G(si_v2) *)tbl + l);
+    const sd_v2 w = *((const KV_G(sd_v2) *)tbl + l);
     r = (w.x | w.y) != 0;
-    if (out) out[k] = si_v4{(uint32_t)g, (uint32_t)(g >> 32), w.x, w.y};
+    if (out) out[k] = sd_v4{(uint32_t)g, (uint32_t)(g >> 32), w.x, w.y};
   }
-  r = si_wave_sum(r);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    si_v2 o = {0, 0};
-    for (uint32_t w = 0; w < SI_TB / 64; w++) o.y += red[w];
-    blk[blockIdx.x] = o;
-  }
+  sd_block_sum(red, {r});
+  if (threadIdx.x == 0) blk[blockIdx.x] = sd_v2{0, sd_block_total(red, 0)};
 }
 
 // ------------------------------------------------------------------------------------------------------ import
@@ -213,22 +138,22 @@ struct si_dev_image {
   const uint8_t *p_dir, *p_inl, *p_ovf;
   uint32_t stride;
   __device__ inline si_dir dir(uint64_t b) const {
-    const si_v4 v = *((const KV_G(si_v4) *)p_dir + b);
+    const sd_v4 v = *((const KV_G(sd_v4) *)p_dir + b);
     return si_dir{(uint64_t)v.x | ((uint64_t)v.y << 32), v.z, v.w};
   }
   __device__ inline void inline_links(uint64_t b, uint32_t &validw, uint32_t &next, uint32_t &head) const {
-    const si_v4 v = *((const KV_G(si_v4) *)(p_inl + b * stride) + SI_LINK_VEC);
+    const sd_v4 v = *((const KV_G(sd_v4) *)(p_inl + b * stride) + SI_LINK_VEC);
     validw = v.x; next = v.y; head = v.z;
   }
   __device__ inline void ovf_links(uint64_t x, uint32_t &validw, uint32_t &next) const {
-    const si_v2 v = *(const KV_G(si_v2) *)(p_ovf + x * stride + KV_VALID_OFF);
+    const sd_v2 v = *(const KV_G(sd_v2) *)(p_ovf + x * stride + KV_VALID_OFF);
     validw = v.x; next = v.y;
   }
 };
 
 // *badw |= what the check found; blk[workgroup] = {0, valid slots}
-__global__ void __launch_bounds__(SI_TB) k_image_check(si_dev_image im, si_geom g, int lock, uint32_t *badw, si_v2 *__restrict__ blk) {
-  __shared__ uint32_t red[SI_TB / 64];
+__global__ void __launch_bounds__(SI_TB) k_image_check(si_dev_image im, si_geom g, int lock, uint32_t *badw, sd_v2 *__restrict__ blk) {
+  __shared__ uint32_t red[SI_TB / 64][1];
   const uint64_t b = (uint64_t)blockIdx.x * SI_TB + threadIdx.x;
   uint32_t bad = 0, r = 0;
   if (b < g.n_buckets) {
@@ -243,14 +168,8 @@ __global__ void __launch_bounds__(SI_TB) k_image_check(si_dev_image im, si_geom 
     }
   }
   if (bad) atomicOr(badw, bad);
-  r = si_wave_sum(r);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    si_v2 o = {0, 0};
-    for (uint32_t w = 0; w < SI_TB / 64; w++) o.y += red[w];
-    blk[blockIdx.x] = o;
-  }
+  sd_block_sum(red, {r});
+  if (threadIdx.x == 0) blk[blockIdx.x] = sd_v2{0, sd_block_total(red, 0)};
 }
 
 // the checked image into the table: bucket id to local bucket id / H, overflow entry x to pool entry base + x
@@ -259,7 +178,7 @@ __global__ void __launch_bounds__(SI_TB) k_image_copy_in(kv_tab t, dint_mod H, u
   constexpr uint32_t VPE = STRIDE / 16, EPS = SI_TB / VPE;
   const uint32_t v = threadIdx.x % VPE;
   const uint64_t e0 = (uint64_t)blockIdx.x * (EPS * SI_UNROLL) + threadIdx.x / VPE, n = n_b + n_ovf;
-  si_v4 x[SI_UNROLL];
+  sd_v4 x[SI_UNROLL];
   uint64_t at[SI_UNROLL];
 #pragma unroll
   for (uint32_t u = 0; u < SI_UNROLL; u++) {
@@ -268,7 +187,7 @@ __global__ void __launch_bounds__(SI_TB) k_image_copy_in(kv_tab t, dint_mod H, u
     if (e >= n) continue;
     const uint8_t *src;
     if (e < n_b) {
-      const uint64_t local = si_div(*((const KV_G(uint64_t) *)(im.p_dir + 16 * e)), H);
+      const uint64_t local = sd_div(*((const KV_G(uint64_t) *)(im.p_dir + 16 * e)), H);
       if (local < t.n_local) at[u] = local;
       src = im.p_inl + e * STRIDE;
     } else {
@@ -276,7 +195,7 @@ __global__ void __launch_bounds__(SI_TB) k_image_copy_in(kv_tab t, dint_mod H, u
       if (p < t.pool_cap) at[u] = t.n_local + p;
       src = im.p_ovf + (e - n_b) * STRIDE;
     }
-    x[u] = __builtin_nontemporal_load((const KV_G(si_v4) *)src + v);
+    x[u] = __builtin_nontemporal_load((const KV_G(sd_v4) *)src + v);
   }
 #pragma unroll
   for (uint32_t u = 0; u < SI_UNROLL; u++) {
@@ -285,7 +204,7 @@ __global__ void __launch_bounds__(SI_TB) k_image_copy_in(kv_tab t, dint_mod H, u
       x[u].y = si_link_in(x[u].y, base);
       if (e0 + u * EPS < n_b) x[u].z = si_link_in(x[u].z, base);
     }
-    *((KV_G(si_v4) *)(t.entries + at[u] * STRIDE) + v) = x[u];
+    *((KV_G(sd_v4) *)(t.entries + at[u] * STRIDE) + v) = x[u];
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) KV_ST(uint32_t, t.pool_top, base + (uint32_t)n_ovf);
 }
@@ -294,8 +213,8 @@ __global__ void __launch_bounds__(SI_TB) k_image_lock_in(uint2 *__restrict__ tbl
   const uint64_t k = (uint64_t)blockIdx.x * SI_TB + threadIdx.x;
   if (k >= n) return;
   const si_dir d = im.dir(k);
-  const uint64_t local = si_div(d.id, H);
-  if (local < n_local) *((KV_G(si_v2) *)tbl + local) = si_v2{d.first, d.count};
+  const uint64_t local = sd_div(d.id, H);
+  if (local < n_local) *((KV_G(sd_v2) *)tbl + local) = sd_v2{d.first, d.count};
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
@@ -317,8 +236,8 @@ void dint_launch_image_count(const dint_kv &kv, const si_sel *sel, dint_image_sc
   for (uint32_t t = 0; t < kv.n_tables; t++) {
     const uint32_t nb = si_blocks(sel[t].n);
     if (nb) {
-      hipLaunchKernelGGL(k_image_count, dim3(nb), dim3(SI_TB), 0, st, kv.h.tab[t], sel[t], (si_v2 *)s.blk + at, (uint32_t *)(s.words + DINT_IMAGE_BAD_AT));
-      hipLaunchKernelGGL(k_image_scan, dim3(1), dim3(1024), 0, st, (const si_v2 *)s.blk + at, nb, s.blk_off + at, s.words + 2 * t);
+      hipLaunchKernelGGL(k_image_count, dim3(nb), dim3(SI_TB), 0, st, kv.h.tab[t], sel[t], (sd_v2 *)s.blk + at, (uint32_t *)(s.words + DINT_IMAGE_BAD_AT));
+      sd_launch_scan((const sd_v2 *)s.blk + at, nb, s.blk_off + at, s.words + 2 * t, st);
     }
     at += nb;
   }
@@ -333,16 +252,16 @@ void dint_launch_image_write(const dint_kv &kv, const si_sel *sel, const si_head
     const uint32_t nb = si_blocks(sel[t].n);
     if (nb) {
       uint8_t *dir = d_buf + it.offset, *img_inl = dir + 16 * it.n_buckets, *img_ovf = img_inl + it.n_buckets * tb.stride;
-      si_v2 *inl = (si_v2 *)s.inl + inl_at;
+      sd_v2 *inl = (sd_v2 *)s.inl + inl_at;
       uint32_t *ovf_src = s.ovf_src + ovf_at;
-      hipLaunchKernelGGL(k_image_dir, dim3(nb), dim3(SI_TB), 0, st, tb, sel[t], (const uint64_t *)s.blk_off + at, (si_v4 *)dir, inl, ovf_src,
+      hipLaunchKernelGGL(k_image_dir, dim3(nb), dim3(SI_TB), 0, st, tb, sel[t], (const uint64_t *)s.blk_off + at, (sd_v4 *)dir, inl, ovf_src,
                          it.n_overflow);
       const uint32_t cb = si_copy_blocks(it.n_buckets + it.n_overflow, tb.stride);
       if (tb.stride == 256)
-        hipLaunchKernelGGL(k_image_copy_out<256>, dim3(cb), dim3(SI_TB), 0, st, tb, sel[t], it.n_overflow, (const si_v2 *)inl,
+        hipLaunchKernelGGL(k_image_copy_out<256>, dim3(cb), dim3(SI_TB), 0, st, tb, sel[t], it.n_overflow, (const sd_v2 *)inl,
                            (const uint32_t *)ovf_src, img_inl, img_ovf);
       else
-        hipLaunchKernelGGL(k_image_copy_out<128>, dim3(cb), dim3(SI_TB), 0, st, tb, sel[t], it.n_overflow, (const si_v2 *)inl,
+        hipLaunchKernelGGL(k_image_copy_out<128>, dim3(cb), dim3(SI_TB), 0, st, tb, sel[t], it.n_overflow, (const sd_v2 *)inl,
                            (const uint32_t *)ovf_src, img_inl, img_ovf);
     }
     at += nb;
@@ -355,8 +274,8 @@ void dint_launch_image_lock_out(const uint2 *tbl, si_sel sel, uint8_t *d_slots, 
   (void)hipMemsetAsync(s.words, 0, DINT_IMAGE_WORDS * sizeof(unsigned long long), st);
   const uint32_t nb = si_blocks(sel.n);
   if (!nb) return;
-  hipLaunchKernelGGL(k_image_lock_out, dim3(nb), dim3(SI_TB), 0, st, tbl, sel, (si_v4 *)d_slots, (si_v2 *)s.blk);
-  hipLaunchKernelGGL(k_image_scan, dim3(1), dim3(1024), 0, st, (const si_v2 *)s.blk, nb, s.blk_off, s.words);
+  hipLaunchKernelGGL(k_image_lock_out, dim3(nb), dim3(SI_TB), 0, st, tbl, sel, (sd_v4 *)d_slots, (sd_v2 *)s.blk);
+  sd_launch_scan((const sd_v2 *)s.blk, nb, s.blk_off, s.words, st);
 }
 
 static si_dev_image si_section(const si_header &h, uint32_t t, const uint8_t *d_buf, bool lock) {
@@ -381,8 +300,8 @@ void dint_launch_image_check(const si_header &h, const uint8_t *d_buf, bool lock
     const uint32_t nb = si_blocks(h.table[t].n_buckets);
     if (nb) {
       hipLaunchKernelGGL(k_image_check, dim3(nb), dim3(SI_TB), 0, st, si_section(h, t, d_buf, lock), si_geometry(h, t), lock ? 1 : 0,
-                         (uint32_t *)(s.words + DINT_IMAGE_BAD_AT), (si_v2 *)s.blk + at);
-      hipLaunchKernelGGL(k_image_scan, dim3(1), dim3(1024), 0, st, (const si_v2 *)s.blk + at, nb, s.blk_off + at, s.words + 2 * t);
+                         (uint32_t *)(s.words + DINT_IMAGE_BAD_AT), (sd_v2 *)s.blk + at);
+      sd_launch_scan((const sd_v2 *)s.blk + at, nb, s.blk_off + at, s.words + 2 * t, st);
     }
     at += nb;
   }
@@ -420,24 +339,6 @@ bool dint_image_shape(uint32_t workload, uint32_t *n_tables, uint32_t *stride, u
 }
 
 // ---- the host form (include/dint_driver.h): the same state_image.h rule over an image in host memory ------------------------
-namespace {
-inline uint32_t ld32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-inline uint64_t ld64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
-struct host_image {
-  const uint8_t *p_dir, *p_inl, *p_ovf;
-  uint32_t stride;
-  si_dir dir(uint64_t b) const { return si_dir{ld64(p_dir + 16 * b), ld32(p_dir + 16 * b + 8), ld32(p_dir + 16 * b + 12)}; }
-  void inline_links(uint64_t b, uint32_t &validw, uint32_t &next, uint32_t &head) const {
-    const uint8_t *e = p_inl + b * stride;
-    validw = ld32(e + KV_VALID_OFF); next = ld32(e + offsetof(kv_hdr, next)); head = ld32(e + offsetof(kv_hdr, head));
-  }
-  void ovf_links(uint64_t x, uint32_t &validw, uint32_t &next) const {
-    const uint8_t *e = p_ovf + x * stride;
-    validw = ld32(e + KV_VALID_OFF); next = ld32(e + offsetof(kv_hdr, next));
-  }
-};
-}  // namespace
-
 extern "C" int dint_state_image_check_host(const void *image, uint64_t bytes) {
   char msg[256];
   auto refuse = [&](const char *what, int table, long long at) {
@@ -457,10 +358,9 @@ extern "C" int dint_state_image_check_host(const void *image, uint64_t bytes) {
   if (uint32_t bad = si_header_check(h, bytes, lock)) return refuse(si_bad_name(bad), -1, 0);
   const uint8_t *p = (const uint8_t *)image;
   for (uint32_t t = 0; t < h.n_tables; t++) {
-    const si_table &it = h.table[t];
-    const host_image im = {p + it.offset, p + it.offset + 16 * it.n_buckets, p + it.offset + 16 * it.n_buckets + (lock ? 0 : it.n_buckets * h.stride), h.stride};
+    const si_host_image im(h, t, p, lock);
     const si_geom g = si_geometry(h, t);
-    for (uint64_t b = 0; b < it.n_buckets; b++) {
+    for (uint64_t b = 0; b < h.table[t].n_buckets; b++) {
       uint64_t rows = 0;
       const uint32_t bad = lock ? si_check_slot(im, b, g) : si_check_bucket(im, b, g, &rows);
       if (bad) return refuse(si_bad_name(bad), (int)t, (long long)b);

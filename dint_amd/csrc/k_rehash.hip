@@ -3,9 +3,9 @@
 // at the end of this file shares).  Table by table:
 //
 //   k_rehash_count    one lane per SOURCE bucket: the valid slots of its chain and the lock words it holds.  Reads the 16-byte
-//                     link vector of the inline header; a chain is walked only where that vector says there is one, to
-//                     KV_MAX_CHAIN steps and with every link checked against the pool's size.  Per workgroup one {rows, locks}
-//   k_rehash_scan     exclusive scan of the workgroups' rows of one table -- the sources' workgroups laid end to end in `srcs`
+//                     link vector of the inline header; a chain is walked only where that vector says there is one, by
+//                     state_image.h si_chain_walk over state_dev.h sd_bucket.  Per workgroup one {rows, locks}
+//   k_state_scan      (state_dev.h) exclusive scan of the workgroups' rows of one table -- the sources' workgroups laid end to end in `srcs`
 //                     order, so a workgroup's offset is its first row's place in SOURCE ORDER -- and the two totals
 //   k_rehash_keys     (the host has read the totals by now)  the count again, a scan inside the workgroup; every valid slot,
 //                     in chain order, becomes a 32-bit sort key -- the destination's local bucket, or n_local for a row that is
@@ -40,106 +40,35 @@
 #include "../../include/dint_driver.h"
 #include "dint_kernels.h"
 #include "dint_kv.h"
+#include "state_dev.h"
 #include "state_image.h"
 #include "state_rehash.h"
 
-#define RH_TB 256u  // threads per workgroup, every kernel here
-
-typedef uint32_t rh_v4 __attribute__((ext_vector_type(4)));
-typedef uint32_t rh_v2 __attribute__((ext_vector_type(2)));
-
-__device__ static inline uint32_t rh_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ static inline uint32_t rh_wave_max(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor(v, d, 64));
-  return v;
-}
+#define RH_TB SD_TB  // threads per workgroup, every kernel here
 
 // ------------------------------------------------------------------------------------------------------ the sources
-// The chain of local bucket b as it lies in a source: on_entry(link, validw) for every entry in chain order, the inline entry
-// (whose link vector lv = {validw, next, head, lockw} the walk starts from) included.  false = the chain does not end within
-// KV_MAX_CHAIN entries, visits its inline entry twice or leaves the pool; nothing is read through such a link.
-template <class F>
-__device__ static inline bool rh_walk(const kv_tab &t, uint64_t b, rh_v4 &lv, F &&on_entry) {
-  lv = *((const KV_G(rh_v4) *)kv_entry_ptr(t, b, KV_INLINE) + SI_LINK_VEC);
-  uint32_t link = lv.z;
-  bool inl = false;
-  for (uint32_t steps = 0; link != KV_NULL; steps++) {
-    if (steps >= KV_MAX_CHAIN) return false;
-    uint32_t validw, next;
-    if (link == KV_INLINE) {
-      if (inl) return false;
-      inl = true;
-      validw = lv.x;
-      next = lv.y;
-    } else {
-      if (link - 2u >= t.pool_cap) return false;
-      const rh_v2 v = *(const KV_G(rh_v2) *)(kv_entry_ptr(t, b, link) + KV_VALID_OFF);
-      validw = v.x;
-      next = v.y;
-    }
-    on_entry(link, validw);
-    link = next;
-  }
-  return true;
+// the valid slots of the chain of bucket ch; false = the chain does not end within KV_MAX_CHAIN entries, visits its inline entry
+// twice or leaves the pool: nothing is read through such a link
+__device__ static inline bool rh_rows(const sd_bucket &ch, uint32_t &rows) {
+  return si_chain_walk(ch.head(), ch, [&](uint32_t, uint32_t, uint32_t validw) {
+    rows += si_valid_count(validw);
+    return true;
+  });
 }
 
-// lock_mode: 0 = none (store), 1 = tatp (the four lock bytes of the inline header), 2 = smallbank (four {num_ex, num_sh} pairs)
+// lock_mode: state_image.h SI_LOCKS_*
 // blk[workgroup] = {valid slots, lock words held} of its 256 buckets; *badw |= 1: a chain that cannot be walked
-__global__ void __launch_bounds__(RH_TB) k_rehash_count(kv_tab t, uint32_t lock_mode, rh_v2 *__restrict__ blk, uint32_t *badw) {
+__global__ void __launch_bounds__(RH_TB) k_rehash_count(kv_tab t, uint32_t lock_mode, sd_v2 *__restrict__ blk, uint32_t *badw) {
   __shared__ uint32_t red[RH_TB / 64][2];
   const uint64_t b = (uint64_t)blockIdx.x * RH_TB + threadIdx.x;
   uint32_t rows = 0, locks = 0;
   if (b < t.n_local) {
-    rh_v4 lv;
-    if (!rh_walk(t, b, lv, [&](uint32_t, uint32_t validw) { rows += si_valid_count(validw); })) atomicOr(badw, 1u);
-    if (lock_mode == 1) {
-      locks = si_valid_count(lv.w);  // (non-zero bytes of the word)
-    } else if (lock_mode == 2) {
-      const KV_G(rh_v4) *c = (const KV_G(rh_v4) *)(kv_entry_ptr(t, b, KV_INLINE) + KV_SB_LOCK_OFF);
-      const rh_v4 c0 = c[0], c1 = c[1];
-      locks = ((c0.x | c0.y) != 0) + ((c0.z | c0.w) != 0) + ((c1.x | c1.y) != 0) + ((c1.z | c1.w) != 0);
-    }
+    const sd_bucket ch = sd_bucket_at(t, b);
+    if (!rh_rows(ch, rows)) atomicOr(badw, 1u);
+    locks = ch.locks_held(lock_mode);
   }
-  rows = rh_wave_sum(rows);
-  locks = rh_wave_sum(locks);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = rows; red[threadIdx.x >> 6][1] = locks; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    rh_v2 o = {0, 0};
-    for (uint32_t w = 0; w < RH_TB / 64; w++) { o.x += red[w][0]; o.y += red[w][1]; }
-    blk[blockIdx.x] = o;
-  }
-}
-
-// off[i] = blk[0].x + .. + blk[i - 1].x; total[0] = the sum of the .x, total[1] = the sum of the .y.  One workgroup of 1,024.
-__global__ void __launch_bounds__(1024) k_rehash_scan(const rh_v2 *__restrict__ blk, uint32_t nb, uint64_t *__restrict__ off,
-                                                      unsigned long long *total) {
-  __shared__ uint64_t part[1024], party[1024];
-  const uint32_t t = threadIdx.x, per = (nb + 1023u) / 1024u;
-  const uint32_t lo = min(nb, t * per), hi = min(nb, lo + per);
-  uint64_t s = 0, sy = 0;
-  for (uint32_t i = lo; i < hi; i++) { s += blk[i].x; sy += blk[i].y; }
-  part[t] = s;
-  party[t] = sy;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {  // inclusive scan of the threads' sums
-    const uint64_t y = t >= d ? part[t - d] : 0, yy = t >= d ? party[t - d] : 0;
-    __syncthreads();
-    part[t] += y;
-    party[t] += yy;
-    __syncthreads();
-  }
-  uint64_t run = part[t] - s;
-  for (uint32_t i = lo; i < hi; i++) {
-    off[i] = run;
-    run += blk[i].x;
-  }
-  if (t == 1023) { total[0] = part[1023]; total[1] = party[1023]; }
+  sd_block_sum(red, {rows, locks});
+  if (threadIdx.x == 0) blk[blockIdx.x] = sd_v2{sd_block_total(red, 0), sd_block_total(red, 1)};
 }
 
 // where the rows of one source go: the destination's bucket count, shard and local buckets
@@ -153,8 +82,7 @@ __device__ static inline uint32_t rh_key(uint64_t key, const rh_dst &d) {
   const uint64_t g = dint_fastmod(dint_hash_key(key), d.size);
   uint64_t local = g;
   if (d.count.d > 1) {
-    uint64_t q = __umul64hi(g, d.count.m);
-    if (g - q * d.count.d >= d.count.d) q++;
+    const uint64_t q = sd_div(g, d.count);
     local = g - q * d.count.d == d.index ? q : SR_FOREIGN;
   }
   return local < d.n_local ? (uint32_t)local : (uint32_t)d.n_local;
@@ -167,19 +95,13 @@ __global__ void __launch_bounds__(RH_TB) k_rehash_keys(kv_tab t, uint32_t src, c
   __shared__ uint32_t red[RH_TB / 64];
   const uint64_t b = (uint64_t)blockIdx.x * RH_TB + threadIdx.x;
   uint32_t rows = 0;
-  rh_v4 lv;
-  bool ok = false;
-  if (b < t.n_local) ok = rh_walk(t, b, lv, [&](uint32_t, uint32_t validw) { rows += si_valid_count(validw); });
-  if (!ok) rows = 0;  // (the count pass has refused such a source already)
-  uint32_t tot;
-  uint32_t before = wave_excl_scan_u32(rows, &tot);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tot;
-  __syncthreads();
-  for (uint32_t v = 0; v < (threadIdx.x >> 6); v++) before += red[v];
+  if (b < t.n_local && !rh_rows(sd_bucket_at(t, b), rows)) rows = 0;  // (the count pass has refused such a source already)
+  const uint32_t before = sd_block_excl_scan(red, rows);
   if (!rows) return;
   uint64_t at = blk_off[blockIdx.x] + before;
-  rh_walk(t, b, lv, [&](uint32_t link, uint32_t validw) {
-    if (!validw) return;
+  const sd_bucket ch = sd_bucket_at(t, b);
+  si_chain_walk(ch.head(), ch, [&](uint32_t, uint32_t link, uint32_t validw) {
+    if (!validw) return true;
     const uint64_t e = link == KV_INLINE ? b : t.n_local + (link - 2u);
     const KV_G(uint64_t) *k = (const KV_G(uint64_t) *)(t.entries + e * t.stride);
 #pragma unroll
@@ -191,6 +113,7 @@ __global__ void __launch_bounds__(RH_TB) k_rehash_keys(kv_tab t, uint32_t src, c
         }
         at++;
       }
+    return true;
   });
 }
 
@@ -217,8 +140,8 @@ __global__ void __launch_bounds__(RH_TB) k_rehash_flags(const uint32_t *__restri
   } else if (p == n) {
     f[p] = 0ull;
   }
-  live = rh_wave_sum(live);
-  entries = rh_wave_max(entries);
+  live = sd_wave_sum_u32(live);
+  entries = sd_wave_max_u32(entries);
   if ((threadIdx.x & 63) == 0) {
     if (live) atomicAdd(w, (unsigned long long)live);
     if (entries) atomicMax(w + 1, (unsigned long long)entries);
@@ -263,7 +186,7 @@ __global__ void __launch_bounds__(RH_TB) k_rehash_build(kv_tab t, const uint32_t
   const uint32_t pool = (uint32_t)scan[p];  // (an overflow entry: its pool index)
   if (b >= t.n_local || (!is_inline && pool >= t.pool_cap)) return;  // (the host has compared the need with the pool: never taken)
   const uint64_t at = is_inline ? (uint64_t)b : t.n_local + pool;
-  rh_v4 o = {0, 0, 0, 0};
+  sd_v4 o = {0, 0, 0, 0};
   if (v < 2) {  // keys of rows 2 v, 2 v + 1
 #pragma unroll
     for (uint32_t h = 0; h < 2; h++) {
@@ -299,7 +222,7 @@ __global__ void __launch_bounds__(RH_TB) k_rehash_build(kv_tab t, const uint32_t
       }
     }
   }
-  *((KV_G(rh_v4) *)(t.entries + at * STRIDE) + v) = o;
+  *((KV_G(sd_v4) *)(t.entries + at * STRIDE) + v) = o;
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
@@ -314,19 +237,18 @@ uint32_t dint_rehash_blocks(const dint_kv *const *srcs, uint32_t n_srcs) {
 
 void dint_launch_rehash_count(const dint_kv *const *srcs, uint32_t n_srcs, dint_rehash_scratch s, hipStream_t st) {
   (void)hipMemsetAsync(s.words, 0, DINT_REHASH_WORDS * sizeof(unsigned long long), st);
-  const uint32_t wl = srcs[0]->workload, lock_mode = wl == DINT_WL_TATP ? 1u : wl == DINT_WL_SMALLBANK ? 2u : 0u;
+  const uint32_t lock_mode = si_lock_mode(srcs[0]->workload);
   uint32_t at = 0;
   for (uint32_t t = 0; t < srcs[0]->n_tables; t++) {
     const uint32_t at0 = at;
     for (uint32_t k = 0; k < n_srcs; k++) {
       const kv_tab &tb = srcs[k]->h.tab[t];
       const uint32_t nb = rh_blocks(tb.n_local);
-      hipLaunchKernelGGL(k_rehash_count, dim3(nb), dim3(RH_TB), 0, st, tb, lock_mode, (rh_v2 *)s.blk + at,
+      hipLaunchKernelGGL(k_rehash_count, dim3(nb), dim3(RH_TB), 0, st, tb, lock_mode, (sd_v2 *)s.blk + at,
                          (uint32_t *)(s.words + DINT_REHASH_BAD_AT));
       at += nb;
     }
-    hipLaunchKernelGGL(k_rehash_scan, dim3(1), dim3(1024), 0, st, (const rh_v2 *)s.blk + at0, at - at0, s.blk_off + at0,
-                       s.words + DINT_REHASH_TABLE_WORDS * t);
+    sd_launch_scan((const sd_v2 *)s.blk + at0, at - at0, s.blk_off + at0, s.words + DINT_REHASH_TABLE_WORDS * t, st);
   }
 }
 

@@ -17,14 +17,16 @@
 //                         bucket contributes, by kind.  Fast path: the two inline headers equal in keys, versions, valid bytes
 //                         and links, no overflow entry, the valid slots' values equal -> nothing, and no chain walk.  Otherwise
 //                         state_sync.h ss_bucket_diff over two chain walkers.  Per workgroup one count.
-//   k_state_scan          exclusive scan of the workgroup counts of all tables (table order, bucket order) on the device
+//   k_state_scan          (state_dev.h) exclusive scan of the workgroup counts of all tables (table order, bucket order) on the device
 //   k_state_diff_write    (launched only when there is something to write: the host has read the total by then, so two engines in
 //                         sync cost ONE pass over their buckets)  the count again, a scan inside the workgroup, and the buckets
 //                         that have records walk a second time and store them: ascending table, ascending bucket, a's rows in a's chain order, then b-only rows in b's
 //   k_state_repair_check  records grouped by bucket? (table, bucket) non-decreasing, table in range
 //   k_state_repair        the first record of every (table, bucket) run owns the bucket and applies the run in order: no two
 //                         lanes ever touch one chain; buckets meet in the pool allocator only, which is atomic
-// Every chain walk counts to KV_MAX_CHAIN and checks its links against the pool's size.
+// Every chain walk counts to KV_MAX_CHAIN and checks its links against the pool's size.  The diff's cursor (ss_chain) is NOT the
+// walk of state_image.h si_chain_walk: it ends quietly at a bad link, and its positions are link << 2 | slot -- the repair
+// relies on both.  Wave and workgroup helpers, the vector type and the scan kernel are state_dev.h's.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -39,14 +41,13 @@
 #include "../../include/dint_driver.h"
 #include "dint_kernels.h"
 #include "dint_kv.h"
+#include "state_dev.h"
 #include "state_sync.h"
 
-#define SS_TB 256u            // threads per workgroup, every kernel here
+#define SS_TB SD_TB           // threads per workgroup, every kernel here
 #define SS_TILE_VEC 1024u     // digest: 16-byte vectors per tile (16 KB)
 #define SS_LDS_PAD 16u        // digest: bytes between entries in LDS (an entry's header would start in bank 0 otherwise)
 #define SS_DIGEST_GRID DINT_STATE_DIGEST_GRID  // digest: workgroups at most (8 per compute unit: what the LDS tiles let stay resident)
-
-typedef uint32_t ss_v4 __attribute__((ext_vector_type(4)));  // a 16-byte vector the compiler knows (address spaces, non-temporal loads)
 
 // device-scope RMWs on the pool words, as the kv kernels (k_kv_dev.h kv_dev_mem)
 struct ss_dev_mem {
@@ -59,29 +60,19 @@ struct ss_dev_mem {
   }
 };
 
-__device__ static inline uint64_t ss_wave_sum_u64(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
-    v += ((uint64_t)hi << 32) | lo;
-  }
-  return v;
-}
-__device__ static inline uint64_t ss_wave_xor_u64(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
-    v ^= ((uint64_t)hi << 32) | lo;
-  }
-  return v;
-}
-__device__ static inline uint32_t ss_wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------------ digest
+// the workgroup's digest of the lanes' d, in thread 0 (every thread calls: the wave, one LDS word per wave and number, one barrier)
+__device__ static inline ss_digest ss_block_digest(uint64_t (&red)[SS_TB / 64][3], ss_digest d) {
+  d.rows = sd_wave_sum_u64(d.rows);
+  d.sum = sd_wave_sum_u64(d.sum);
+  d.xr = sd_wave_xor_u64(d.xr);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = d.rows; red[threadIdx.x >> 6][1] = d.sum; red[threadIdx.x >> 6][2] = d.xr; }
+  __syncthreads();
+  ss_digest w = {0, 0, 0};
+  if (threadIdx.x == 0)
+    for (uint32_t k = 0; k < SS_TB / 64; k++) ss_digest_merge(w, ss_digest{red[k][0], red[k][1], red[k][2]});
+  return w;
+}
 // STRIDE = bytes per entry (256: 40-byte values, 128: 8-byte values).  part[4 * workgroup ..] = {rows, sum, xor, 0} of what
 // this workgroup read.
 template <uint32_t STRIDE>
@@ -90,22 +81,22 @@ __global__ void __launch_bounds__(SS_TB) k_state_digest(kv_tab t, uint32_t table
   constexpr uint32_t EPT = SS_TILE_VEC / VPE;       // entries per tile
   constexpr uint32_t LSTRIDE = STRIDE + SS_LDS_PAD; // an entry's distance in LDS
   constexpr uint32_t VS = STRIDE == 256 ? 40u : 8u;
-  __shared__ ss_v4 Lv[EPT * LSTRIDE / 16];
+  __shared__ sd_v4 Lv[EPT * LSTRIDE / 16];
   __shared__ uint64_t red[SS_TB / 64][3];
   const uint8_t *L = (const uint8_t *)Lv;
   const uint32_t tid = threadIdx.x;
   const uint32_t top = *(const volatile uint32_t *)t.pool_top;  // (a failed insert may have left it above the pool's size for a moment)
   const uint64_t n_ent = t.n_local + (uint64_t)(top < t.pool_cap ? top : t.pool_cap);
   const uint64_t n_vec = n_ent * VPE, n_tiles = (n_ent + EPT - 1) / EPT;
-  const KV_G(ss_v4) *src = (const KV_G(ss_v4) *)t.entries;
+  const KV_G(sd_v4) *src = (const KV_G(sd_v4) *)t.entries;
   ss_digest d = {0, 0, 0};
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const uint64_t v0 = tile * SS_TILE_VEC;
-    ss_v4 v[SS_TILE_VEC / SS_TB];
+    sd_v4 v[SS_TILE_VEC / SS_TB];
 #pragma unroll
     for (uint32_t k = 0; k < SS_TILE_VEC / SS_TB; k++) {
       const uint64_t g = v0 + k * SS_TB + tid;
-      v[k] = g < n_vec ? __builtin_nontemporal_load(src + g) : (ss_v4)(0u);
+      v[k] = g < n_vec ? __builtin_nontemporal_load(src + g) : (sd_v4)(0u);
     }
 #pragma unroll
     for (uint32_t k = 0; k < SS_TILE_VEC / SS_TB; k++) {
@@ -124,14 +115,8 @@ __global__ void __launch_bounds__(SS_TB) k_state_digest(kv_tab t, uint32_t table
     }
     __syncthreads();
   }
-  d.rows = ss_wave_sum_u64(d.rows);
-  d.sum = ss_wave_sum_u64(d.sum);
-  d.xr = ss_wave_xor_u64(d.xr);
-  if ((tid & 63) == 0) { red[tid >> 6][0] = d.rows; red[tid >> 6][1] = d.sum; red[tid >> 6][2] = d.xr; }
-  __syncthreads();
+  const ss_digest w = ss_block_digest(red, d);
   if (tid == 0) {
-    ss_digest w = {0, 0, 0};
-    for (uint32_t k = 0; k < SS_TB / 64; k++) ss_digest_merge(w, ss_digest{red[k][0], red[k][1], red[k][2]});
     unsigned long long *o = part + 4 * (size_t)blockIdx.x;
     o[0] = w.rows; o[1] = w.sum; o[2] = w.xr; o[3] = 0;
   }
@@ -147,14 +132,8 @@ __global__ void __launch_bounds__(SS_TB) k_state_digest_sum(const unsigned long 
   const unsigned long long *p = part + (size_t)4 * SS_DIGEST_GRID * table;
   ss_digest d = {0, 0, 0};
   for (uint32_t k = tid; k < cnt.n[table]; k += SS_TB) ss_digest_merge(d, ss_digest{p[4 * k], p[4 * k + 1], p[4 * k + 2]});
-  d.rows = ss_wave_sum_u64(d.rows);
-  d.sum = ss_wave_sum_u64(d.sum);
-  d.xr = ss_wave_xor_u64(d.xr);
-  if ((tid & 63) == 0) { red[tid >> 6][0] = d.rows; red[tid >> 6][1] = d.sum; red[tid >> 6][2] = d.xr; }
-  __syncthreads();
+  const ss_digest w = ss_block_digest(red, d);
   if (tid == 0) {
-    ss_digest w = {0, 0, 0};
-    for (uint32_t k = 0; k < SS_TB / 64; k++) ss_digest_merge(w, ss_digest{red[k][0], red[k][1], red[k][2]});
     out[4 * table] = w.rows; out[4 * table + 1] = w.sum; out[4 * table + 2] = w.xr; out[4 * table + 3] = 0;
   }
 }
@@ -230,8 +209,8 @@ struct ss_write_emit {
 template <uint32_t VS>
 __device__ static inline bool ss_bucket_equal_fast(const kv_tab &ta, const kv_tab &tb, uint64_t b) {
   const uint8_t *ea = kv_entry_ptr(ta, b, KV_INLINE), *eb = kv_entry_ptr(tb, b, KV_INLINE);
-  const KV_G(ss_v4) *pa = (const KV_G(ss_v4) *)ea, *pb = (const KV_G(ss_v4) *)eb;
-  const ss_v4 a0 = pa[0], a1 = pa[1], a2 = pa[2], a3 = pa[3], b0 = pb[0], b1 = pb[1], b2 = pb[2], b3 = pb[3];
+  const KV_G(sd_v4) *pa = (const KV_G(sd_v4) *)ea, *pb = (const KV_G(sd_v4) *)eb;
+  const sd_v4 a0 = pa[0], a1 = pa[1], a2 = pa[2], a3 = pa[3], b0 = pb[0], b1 = pb[1], b2 = pb[2], b3 = pb[3];
   const uint32_t d = (a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) |
                      (a1.w ^ b1.w) | (a2.x ^ b2.x) | (a2.y ^ b2.y) | (a2.z ^ b2.z) | (a2.w ^ b2.w) | (a3.x ^ b3.x) | (a3.y ^ b3.y) |
                      (a3.z ^ b3.z);  // keys, versions, valid bytes, next, head (not the lock bytes)
@@ -262,44 +241,15 @@ __global__ void __launch_bounds__(SS_TB) k_state_diff_count(kv_tab ta, kv_tab tb
   __shared__ uint32_t red[SS_TB / 64][4];
   const uint64_t b = (uint64_t)blockIdx.x * SS_TB + threadIdx.x;
   const uint64_t packed = b < ta.n_local ? ss_bucket_count<VS>(ta, tb, b) : 0;
-  uint32_t c[4];
-#pragma unroll
-  for (uint32_t k = 0; k < 4; k++) c[k] = ss_wave_sum_u32((uint32_t)(packed >> (16 * k)) & 0xFFFFu);
-  if ((threadIdx.x & 63) == 0)
-    for (uint32_t k = 0; k < 4; k++) red[threadIdx.x >> 6][k] = c[k];
-  __syncthreads();
+  sd_block_sum(red, {(uint32_t)packed & 0xFFFFu, (uint32_t)(packed >> 16) & 0xFFFFu, (uint32_t)(packed >> 32) & 0xFFFFu,
+                     (uint32_t)(packed >> 48)});
   if (threadIdx.x < 4) {
-    uint32_t s = 0;
-    for (uint32_t w = 0; w < SS_TB / 64; w++) s += red[w][threadIdx.x];
+    const uint32_t s = sd_block_total(red, threadIdx.x);
     if (s) atomicAdd(stats + threadIdx.x, (unsigned long long)s);
     red[0][threadIdx.x] = s;
   }
   __syncthreads();
   if (threadIdx.x == 0) cnt[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-}
-
-// off[i] = cnt[0] + .. + cnt[i - 1]; *total = the sum.  One workgroup of 1,024.
-__global__ void __launch_bounds__(1024) k_state_scan(const uint32_t *__restrict__ cnt, uint32_t nb, uint64_t *__restrict__ off,
-                                                     unsigned long long *total) {
-  __shared__ uint64_t part[1024];
-  const uint32_t t = threadIdx.x, per = (nb + 1023u) / 1024u;
-  const uint32_t lo = min(nb, t * per), hi = min(nb, lo + per);
-  uint64_t s = 0;
-  for (uint32_t i = lo; i < hi; i++) s += cnt[i];
-  part[t] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {  // inclusive scan of the threads' sums
-    const uint64_t y = t >= d ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += y;
-    __syncthreads();
-  }
-  uint64_t run = part[t] - s;
-  for (uint32_t i = lo; i < hi; i++) {
-    off[i] = run;
-    run += cnt[i];
-  }
-  if (t == 1023) *total = part[1023];
 }
 
 template <uint32_t VS>
@@ -312,11 +262,7 @@ __global__ void __launch_bounds__(SS_TB) k_state_diff_write(kv_tab ta, kv_tab tb
   const uint64_t packed = b < ta.n_local ? ss_bucket_count<VS>(ta, tb, b) : 0;
   const uint32_t mine = (uint32_t)(packed & 0xFFFFu) + (uint32_t)((packed >> 16) & 0xFFFFu) + (uint32_t)((packed >> 32) & 0xFFFFu) +
                         (uint32_t)(packed >> 48);
-  uint32_t tot;
-  uint32_t before = wave_excl_scan_u32(mine, &tot);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tot;
-  __syncthreads();
-  for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) before += red[w];
+  const uint32_t before = sd_block_excl_scan(red, mine);
   if (mine == 0 || at0 + before >= cap) return;
   const ss_chain ca = {ta, b}, cb = {tb, b};
   ss_write_emit<VS> em = {out, at0 + before, cap, table};
@@ -383,7 +329,7 @@ __global__ void __launch_bounds__(SS_TB) k_state_repair(const uint8_t *__restric
   }
 #pragma unroll
   for (uint32_t k = 0; k < 4; k++) {
-    const uint32_t s = ss_wave_sum_u32(c[k]);
+    const uint32_t s = sd_wave_sum_u32(c[k]);
     if ((threadIdx.x & 63) == 0 && s) {
       atomicAdd(out + k, (unsigned long long)s);
       if (k == 3) atomicAdd(&stats->pool_exhausted, (unsigned long long)s);
@@ -424,7 +370,7 @@ void dint_launch_state_diff_count(const dint_kv &a, const dint_kv &b, dint_state
     else hipLaunchKernelGGL(k_state_diff_count<8>, dim3(nb), dim3(SS_TB), 0, st, ta, tb, s.blk_cnt + at, s.words);
     at += nb;
   }
-  hipLaunchKernelGGL(k_state_scan, dim3(1), dim3(1024), 0, st, (const uint32_t *)s.blk_cnt, at, s.blk_off, s.words + 4);
+  sd_launch_scan((const uint32_t *)s.blk_cnt, at, s.blk_off, s.words + 4, st);
 }
 
 void dint_launch_state_diff_write(const dint_kv &a, const dint_kv &b, dint_state_scratch s, void *d_records, uint64_t cap, hipStream_t st) {
@@ -455,10 +401,8 @@ void dint_launch_state_repair(const dint_kv &kv, const void *d_records, uint64_t
 
 // ---- the host forms (include/dint_driver.h): the same state_sync.h functions over dumped rows -------------------------
 namespace {
-inline uint64_t ld64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
-inline uint32_t ld32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
 inline uint64_t host_row_hash(uint64_t key, uint32_t ver, uint32_t table, const uint8_t *val, uint32_t val_size) {
-  return ss_row_hash(key, ver, table, val_size, [val](uint32_t k) { return ld64(val + 8 * k); });
+  return ss_row_hash(key, ver, table, val_size, [val](uint32_t k) { return si_ld64(val + 8 * k); });
 }
 // the rows of one bucket out of a dump: idx[lo .. hi) index the dumped arrays, in dump (= chain) order
 struct host_rows {
@@ -474,7 +418,7 @@ struct host_rows {
   bool same(uint64_t p, uint64_t q) const { return p == q; }
   uint64_t key(uint64_t p) const { return keys[idx[p]]; }
   uint32_t ver(uint64_t p) const { return vers[idx[p]]; }
-  uint32_t val32(uint64_t p, uint32_t w) const { return ld32(vals + idx[p] * val_size + 4 * w); }
+  uint32_t val32(uint64_t p, uint32_t w) const { return si_ld32(vals + idx[p] * val_size + 4 * w); }
   uint64_t find(uint64_t k) const {
     for (uint64_t p = 0; p < n; p++)
       if (keys[idx[p]] == k) return p;

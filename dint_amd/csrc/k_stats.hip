@@ -2,8 +2,8 @@
 // driven by engine.hip; the rule lives in state_stats.h, which the host form at the end of this file shares).
 //
 //   k_state_stats      one lane per bucket, the workgroups striding over the table (DINT_STATE_STATS_GRID at most).  A lane
-//                      loads the 16-byte link vector of the inline header and walks the chain from it as rh_walk (k_rehash.hip)
-//                      does: header sectors only, 8 bytes {validw, next} per overflow entry, values never.  Key vectors are
+//                      loads the 16-byte link vector of the inline header and walks the chain from it (state_dev.h sd_bucket
+//                      under state_image.h si_chain_walk): header sectors only, 8 bytes {validw, next} per overflow entry, values never.  Key vectors are
 //                      loaded only by a bucket of more than one valid slot, for the duplicate comparison, which re-walks (no
 //                      per-lane array).  The counters stay in registers until the workgroup has run out of buckets; the two
 //                      histograms go to one LDS array per WAVE -- the lanes that share a bin are found with a ballot and one
@@ -22,10 +22,11 @@
 #include "../../include/dint_driver.h"
 #include "dint_kernels.h"
 #include "dint_kv.h"
+#include "state_dev.h"
 #include "state_image.h"
 #include "state_stats.h"
 
-#define ST_TB 256u       // threads per workgroup of k_state_stats
+#define ST_TB SD_TB      // threads per workgroup of k_state_stats
 #define ST_SUM_TB 1024u  // ... of k_state_stats_sum: 8 groups of 128 threads, thread w of a group word w
 #define ST_GRID DINT_STATE_STATS_GRID
 
@@ -34,24 +35,6 @@ static_assert(offsetof(dint_table_stats, chain_hist) == 8 * ST_CHAIN_HIST && off
               offsetof(dint_table_stats, reserved) == 8 * ST_BAD && offsetof(dint_table_stats, pool_top) == 8 * ST_POOL_TOP &&
               offsetof(dint_table_stats, longest_chain_bucket) == 8 * ST_LONGEST_BUCKET && offsetof(dint_table_stats, locks_held) == 8 * ST_LOCKS,
               "the words of state_stats.h are the fields of dint_table_stats");
-
-typedef uint32_t st_v4 __attribute__((ext_vector_type(4)));
-typedef uint32_t st_v2 __attribute__((ext_vector_type(2)));
-
-__device__ static inline uint64_t st_shfl_xor_u64(uint64_t v, int d) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ static inline uint64_t st_wave_sum(uint64_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += st_shfl_xor_u64(v, d);
-  return v;
-}
-__device__ static inline uint32_t st_wave_max(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor(v, d, 64));
-  return v;
-}
 
 // h[bin] += the active lanes of this wave that hold `bin` (h: this wave's own LDS array; every lane of the wave calls).  One
 // round per distinct bin among the lanes -- mostly one or two: neighbouring buckets look alike.
@@ -67,38 +50,11 @@ __device__ static inline void st_hist_add(st_lds_u32 *h, uint32_t bin, bool acti
   }
 }
 
-// local bucket b as it lies in the table: lv = the inline header's {validw, next, head, lockw}
-struct st_dev_chain {
-  const kv_tab &t;
-  uint64_t b;
-  st_v4 lv;
-  __device__ inline uint32_t head() const { return lv.z; }
-  __device__ inline bool link_ok(uint32_t link) const { return link - 2u < t.pool_cap; }
-  __device__ inline void links(uint32_t link, uint32_t &validw, uint32_t &next) const {
-    if (link == KV_INLINE) {
-      validw = lv.x;
-      next = lv.y;
-    } else {
-      const st_v2 v = *(const KV_G(st_v2) *)(kv_entry_ptr(t, b, link) + KV_VALID_OFF);
-      validw = v.x;
-      next = v.y;
-    }
-  }
-  __device__ inline void keys(uint32_t link, uint64_t k[4]) const {
-    const KV_G(st_v4) *p = (const KV_G(st_v4) *)kv_entry_ptr(t, b, link);
-    const st_v4 a = p[0], c = p[1];
-    k[0] = (uint64_t)a.x | ((uint64_t)a.y << 32);
-    k[1] = (uint64_t)a.z | ((uint64_t)a.w << 32);
-    k[2] = (uint64_t)c.x | ((uint64_t)c.y << 32);
-    k[3] = (uint64_t)c.z | ((uint64_t)c.w << 32);
-  }
-};
-
 // the sums a lane keeps, in the order they are reduced (red[wave][k]); then the maxima
 enum : uint32_t { SL_BUCKETS = 0, SL_EMPTY, SL_ROWS, SL_ENTRIES, SL_OVERFLOW, SL_FIRST, SL_UNLINKED, SL_HIT, SL_SHADOWED, SL_UNCHECKED,
                   SL_LOCKS, SL_BAD, SL_SUMS, SL_LONGEST = SL_SUMS, SL_LONGEST_ID, SL_MOST, SL_N };
 
-// lock_mode: 0 = none (store), 1 = tatp (the four lock bytes of the inline header), 2 = smallbank (four {num_ex, num_sh} pairs)
+// lock_mode: state_image.h SI_LOCKS_*
 // part[ST_WORDS * workgroup ..] = the report of the buckets this workgroup walked (state_stats.h words; holes and the pool words 0)
 __global__ void __launch_bounds__(ST_TB) k_state_stats(kv_tab t, uint32_t lock_mode, uint32_t shard_index, uint32_t shard_count,
                                                        unsigned long long *__restrict__ part) {
@@ -121,17 +77,10 @@ __global__ void __launch_bounds__(ST_TB) k_state_stats(kv_tab t, uint32_t lock_m
     uint32_t cbin = 0, rbin = 0;
     bool counted = false;
     if (active) {
-      const st_dev_chain ch = {t, b, *((const KV_G(st_v4) *)kv_entry_ptr(t, b, KV_INLINE) + SI_LINK_VEC)};
+      const sd_bucket ch = sd_bucket_at(t, b);
       const st_bucket r = st_bucket_walk(ch);
       n_b++;
-      if (lock_mode == 1) {
-        locks += st_locks_tatp(ch.lv.w);
-      } else if (lock_mode == 2) {
-        const KV_G(st_v4) *c = (const KV_G(st_v4) *)(kv_entry_ptr(t, b, KV_INLINE) + KV_SB_LOCK_OFF);
-        const st_v4 c0 = c[0], c1 = c[1];
-        const uint32_t cw[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        locks += st_locks_smallbank(cw);
-      }
+      locks += ch.locks_held(lock_mode);
       counted = r.ok;
       if (r.ok) {
         empty += r.rows == 0;
@@ -162,12 +111,12 @@ __global__ void __launch_bounds__(ST_TB) k_state_stats(kv_tab t, uint32_t lock_m
   const uint64_t s[SL_SUMS] = {n_b, empty, rows, entries, overflow, first, unlinked, hit, shadowed, unchecked, locks, bad};
   uint64_t ws[SL_SUMS];
 #pragma unroll
-  for (uint32_t k = 0; k < SL_SUMS; k++) ws[k] = st_wave_sum(s[k]);
-  most = st_wave_max(most);
+  for (uint32_t k = 0; k < SL_SUMS; k++) ws[k] = sd_wave_sum_u64(s[k]);
+  most = sd_wave_max_u32(most);
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {
     const uint32_t oc = __shfl_xor(longest, d, 64);
-    const uint64_t oi = st_shfl_xor_u64(longest_id, d);
+    const uint64_t oi = sd_shfl_xor_u64(longest_id, d);
     if (st_longer(oc, oi, longest, longest_id)) {
       longest = oc;
       longest_id = oi;
@@ -263,7 +212,7 @@ __global__ void __launch_bounds__(ST_SUM_TB) k_state_stats_sum(const unsigned lo
 
 // ------------------------------------------------------------------------------------------------------ host side
 void dint_launch_state_stats(const dint_kv &kv, dint_stats_scratch s, hipStream_t st) {
-  const uint32_t wl = kv.workload, lock_mode = wl == DINT_WL_TATP ? 1u : wl == DINT_WL_SMALLBANK ? 2u : 0u;
+  const uint32_t lock_mode = si_lock_mode(kv.workload);
   st_sum_args a;
   memset(&a, 0, sizeof a);
   for (uint32_t t = 0; t < kv.n_tables; t++) {
@@ -280,29 +229,6 @@ void dint_launch_state_stats(const dint_kv &kv, dint_stats_scratch s, hipStream_
 }
 
 // ---- the host form (include/dint_driver.h): the same state_stats.h rule over an image in host memory -----------------------
-namespace {
-inline uint32_t ld32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-inline uint64_t ld64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
-// bucket b of a checked image: links are image-relative, k >= 2 = overflow entry k - 2 of the table's section
-struct host_chain {
-  const uint8_t *inl, *p_ovf;
-  uint32_t stride;
-  uint64_t n_overflow;
-  const uint8_t *entry(uint32_t link) const { return link == KV_INLINE ? inl : p_ovf + (uint64_t)(link - 2u) * stride; }
-  uint32_t head() const { return ld32(inl + offsetof(kv_hdr, head)); }
-  bool link_ok(uint32_t link) const { return (uint64_t)link - 2u < n_overflow; }
-  void links(uint32_t link, uint32_t &validw, uint32_t &next) const {
-    const uint8_t *e = entry(link);
-    validw = ld32(e + KV_VALID_OFF);
-    next = ld32(e + offsetof(kv_hdr, next));
-  }
-  void keys(uint32_t link, uint64_t k[4]) const {
-    const uint8_t *e = entry(link);
-    for (uint32_t i = 0; i < 4; i++) k[i] = ld64(e + 8 * i);
-  }
-};
-}  // namespace
-
 extern "C" int dint_state_stats_image_host(const void *image, uint64_t bytes, dint_table_stats *out, uint32_t cap_tables) {
   if (!out) {
     dint_set_last_error("null argument");
@@ -321,24 +247,19 @@ extern "C" int dint_state_stats_image_host(const void *image, uint64_t bytes, di
     dint_set_last_error(msg);
     return DINT_EINVAL;
   }
-  const uint32_t lock_mode = h.workload == DINT_WL_TATP ? 1u : h.workload == DINT_WL_SMALLBANK ? 2u : 0u;
-  const uint8_t *p = (const uint8_t *)image;
+  const uint32_t lock_mode = si_lock_mode(h.workload);
   for (uint32_t t = 0; t < h.n_tables; t++) {
-    const si_table &it = h.table[t];
-    const uint8_t *p_dir = p + it.offset, *p_inl = p_dir + 16 * it.n_buckets, *p_ovf = p_inl + it.n_buckets * h.stride;
+    const si_host_image im(h, t, (const uint8_t *)image, false);
     uint64_t w[ST_WORDS];
     st_report_init(w);
-    for (uint64_t b = 0; b < it.n_buckets; b++) {
-      const host_chain ch = {p_inl + b * h.stride, p_ovf, h.stride, it.n_overflow};
-      uint32_t locks = 0;
-      if (lock_mode == 1) {
-        locks = st_locks_tatp(ld32(ch.inl + KV_LOCKB_OFF));
-      } else if (lock_mode == 2) {
-        uint32_t cw[8];
-        for (uint32_t k = 0; k < 8; k++) cw[k] = ld32(ch.inl + KV_SB_LOCK_OFF + 4 * k);
-        locks = st_locks_smallbank(cw);
-      }
-      st_report_add(w, st_bucket_walk(ch), ld64(p_dir + 16 * b), locks);
+    for (uint64_t b = 0; b < h.table[t].n_buckets; b++) {
+      uint32_t bad = 0;  // (the check has judged every link already: stays 0)
+      const si_image_chain<si_host_image> ch = {im, b, im.dir(b), &bad};
+      const uint8_t *inl = im.entry(b, KV_INLINE);
+      const uint32_t locks = si_locks_held(lock_mode, si_ld32(inl + KV_LOCKB_OFF), [inl](uint32_t c[8]) {
+        for (uint32_t k = 0; k < 8; k++) c[k] = si_ld32(inl + KV_SB_LOCK_OFF + 4 * k);
+      });
+      st_report_add(w, st_bucket_walk(ch), ch.d.id, locks);
     }
     if (st_report_finish(w, 0)) {  // (the check has walked every chain already: never taken)
       snprintf(msg, sizeof msg, "a chain of table %u cannot be walked", t);

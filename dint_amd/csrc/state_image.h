@@ -29,7 +29,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
+#include "../../include/dint_abi.h"
 #include "dint_kv_core.h"
 
 #if defined(__HIPCC__)
@@ -97,6 +99,25 @@ SI_HD static inline const char *si_bad_name(uint32_t bad) {
 SI_HD static inline uint32_t si_valid_count(uint32_t validw) {
   return ((validw & 0xFFu) != 0) + ((validw & 0xFF00u) != 0) + ((validw & 0xFF0000u) != 0) + ((validw & 0xFF000000u) != 0);
 }
+// lock words live in the inline header of a bucket, and where depends on the workload
+enum : uint32_t {
+  SI_LOCKS_NONE = 0,      // store
+  SI_LOCKS_TATP = 1,      // the four lock bytes of the header's word at KV_LOCKB_OFF
+  SI_LOCKS_SMALLBANK = 2  // four {num_ex, num_sh} pairs at KV_SB_LOCK_OFF
+};
+SI_HD static inline uint32_t si_lock_mode(uint32_t workload) {
+  return workload == DINT_WL_TATP ? SI_LOCKS_TATP : workload == DINT_WL_SMALLBANK ? SI_LOCKS_SMALLBANK : SI_LOCKS_NONE;
+}
+// lock words held by one inline header: non-zero tatp lock bytes of `lockw` / smallbank pairs with a non-zero word
+// (counters(c) fills c[8] with the header's eight counter words; only called for smallbank)
+template <class C>
+SI_HD static inline uint32_t si_locks_held(uint32_t lock_mode, uint32_t lockw, C &&counters) {
+  if (lock_mode == SI_LOCKS_TATP) return si_valid_count(lockw);  // (non-zero bytes of the word)
+  if (lock_mode != SI_LOCKS_SMALLBANK) return 0;
+  uint32_t c[8];
+  counters(c);
+  return ((c[0] | c[1]) != 0) + ((c[2] | c[3]) != 0) + ((c[4] | c[5]) != 0) + ((c[6] | c[7]) != 0);
+}
 SI_HD static inline uint64_t si_gcd(uint64_t a, uint64_t b) {
   while (b) { const uint64_t r = a % b; a = b; b = r; }
   return a;
@@ -160,8 +181,31 @@ SI_HD static inline uint32_t si_inline_next_out(uint32_t src_next, bool linked, 
 SI_HD static inline uint32_t si_link_in(uint32_t link, uint32_t base) { return link >= 2u ? link + base : link; }
 
 // ---- one chain, wherever it lies --------------------------------------------------------------------------------------
-// E: bool link_ok(link) for a link >= 2; void load(link, validw, next) for link 1 or an accepted link >= 2.
-// on_ovf(m, link): the m-th overflow entry of the chain; false stops the walk.
+// THE walk of a bucket's chain, for tables in HBM and images alike: from `head` to KV_NULL, KV_MAX_CHAIN entries at most, the
+// inline entry (link KV_INLINE) an ordinary chain node wherever it sits and visited at most once, every other link accepted
+// by its owner before anything is read through it.
+// E: bool link_ok(link) for a link >= 2; void links(link, validw, next) for link 1 or an accepted link >= 2.
+// on_entry(pos, link, validw): entry number `pos` of the chain; false stops the walk.  Returns whether the end was reached.
+template <class E, class F>
+SI_HD static inline bool si_chain_walk(uint32_t head, const E &e, F &&on_entry) {
+  uint32_t link = head;
+  bool inl = false;
+  for (uint32_t pos = 0; link != KV_NULL; pos++) {
+    if (pos >= KV_MAX_CHAIN) return false;
+    if (link == KV_INLINE) {
+      if (inl) return false;
+      inl = true;
+    } else if (!e.link_ok(link)) {
+      return false;
+    }
+    uint32_t validw, next;
+    e.links(link, validw, next);
+    if (!on_entry(pos, link, validw)) return false;
+    link = next;
+  }
+  return true;
+}
+// ... as the image sees it.  on_ovf(m, link): the m-th overflow entry of the chain; false stops the walk.
 struct si_walk {
   uint32_t count;    // overflow entries visited
   uint32_t before;   // ... of them ahead of the inline entry
@@ -172,22 +216,17 @@ struct si_walk {
 template <class E, class F>
 SI_HD static inline si_walk si_walk_chain(uint32_t head, const E &e, F &&on_ovf) {
   si_walk w = {0, 0, 0, 0, 1};
-  uint32_t link = head;
-  for (uint32_t steps = 0; link != KV_NULL; steps++) {
-    if (steps >= KV_MAX_CHAIN) { w.ok = 0; break; }
+  w.ok = si_chain_walk(head, e, [&](uint32_t, uint32_t link, uint32_t validw) {
     if (link == KV_INLINE) {
-      if (w.linked) { w.ok = 0; break; }
       w.linked = 1;
       w.before = w.count;
     } else {
-      if (!e.link_ok(link) || !on_ovf(w.count, link)) { w.ok = 0; break; }
+      if (!on_ovf(w.count, link)) return false;
       w.count++;
     }
-    uint32_t validw, next;
-    e.load(link, validw, next);
     w.rows += si_valid_count(validw);
-    link = next;
-  }
+    return true;
+  });
   return w;
 }
 
@@ -210,25 +249,34 @@ SI_HD static inline uint32_t si_check_slot(const A &a, uint64_t b, const si_geom
   return si_check_id(d.id, b > 0, b > 0 ? a.dir(b - 1).id : 0, g);
 }
 // bucket b of a kv table.  A: si_dir dir(b); void inline_links(b, validw, next, head); void ovf_links(x, validw, next)
-// (x < n_overflow: never called with another).  *rows += the valid slots of the bucket's chain.
+// (x < n_overflow: never called with another); for the table report also void keys(b, link, k[4]).
+// The bucket's chain as si_chain_walk and state_stats.h st_bucket_walk take it: a link is good inside the bucket's own run,
+// and *bad records one that is not.
 template <class A>
 struct si_image_chain {
   const A &a;
   uint64_t b;
   si_dir d;
   uint32_t *bad;
+  SI_HD inline uint32_t head() const {
+    uint32_t validw, next, head;
+    a.inline_links(b, validw, next, head);
+    return head;
+  }
   SI_HD inline bool link_ok(uint32_t link) const {
     const uint64_t x = (uint64_t)link - 2u;
     if (x >= d.first && x < (uint64_t)d.first + d.count) return true;
     *bad |= SI_BAD_LINK;
     return false;
   }
-  SI_HD inline void load(uint32_t link, uint32_t &validw, uint32_t &next) const {
+  SI_HD inline void links(uint32_t link, uint32_t &validw, uint32_t &next) const {
     uint32_t head;
     if (link == KV_INLINE) a.inline_links(b, validw, next, head);
     else a.ovf_links((uint64_t)link - 2u, validw, next);
   }
+  SI_HD inline void keys(uint32_t link, uint64_t k[4]) const { a.keys(b, link, k); }
 };
+// *rows += the valid slots of the bucket's chain.
 template <class A>
 SI_HD static inline uint32_t si_check_bucket(const A &a, uint64_t b, const si_geom &g, uint64_t *rows) {
   const si_dir d = a.dir(b);
@@ -254,3 +302,30 @@ SI_HD static inline uint32_t si_check_bucket(const A &a, uint64_t b, const si_ge
   *rows += w.rows;
   return bad;
 }
+
+// ---- an image in host memory ---------------------------------------------------------------------------------------------
+static inline uint32_t si_ld32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
+static inline uint64_t si_ld64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
+// table t's section of an image whose header h has passed si_header_check: the A of si_check_slot / si_check_bucket /
+// si_image_chain over plain bytes at any alignment
+struct si_host_image {
+  const uint8_t *p_dir, *p_inl, *p_ovf;
+  uint32_t stride;
+  si_host_image(const si_header &h, uint32_t t, const uint8_t *image, bool lock)
+      : p_dir(image + h.table[t].offset), p_inl(p_dir + 16 * h.table[t].n_buckets),
+        p_ovf(lock ? p_inl : p_inl + h.table[t].n_buckets * h.stride), stride(h.stride) {}
+  const uint8_t *entry(uint64_t b, uint32_t link) const { return link == KV_INLINE ? p_inl + b * stride : p_ovf + (uint64_t)(link - 2u) * stride; }
+  si_dir dir(uint64_t b) const { return si_dir{si_ld64(p_dir + 16 * b), si_ld32(p_dir + 16 * b + 8), si_ld32(p_dir + 16 * b + 12)}; }
+  void inline_links(uint64_t b, uint32_t &validw, uint32_t &next, uint32_t &head) const {
+    const uint8_t *e = entry(b, KV_INLINE);
+    validw = si_ld32(e + KV_VALID_OFF); next = si_ld32(e + offsetof(kv_hdr, next)); head = si_ld32(e + offsetof(kv_hdr, head));
+  }
+  void ovf_links(uint64_t x, uint32_t &validw, uint32_t &next) const {
+    const uint8_t *e = p_ovf + x * stride;
+    validw = si_ld32(e + KV_VALID_OFF); next = si_ld32(e + offsetof(kv_hdr, next));
+  }
+  void keys(uint64_t b, uint32_t link, uint64_t k[4]) const {
+    const uint8_t *e = entry(b, link);
+    for (uint32_t i = 0; i < 4; i++) k[i] = si_ld64(e + 8 * i);
+  }
+};

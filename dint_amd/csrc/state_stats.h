@@ -2,10 +2,11 @@
 // include/dint_abi.h) and the host form over a state image (dint_state_stats_image_host, include/dint_driver.h), as
 // state_image.h is for the image and state_rehash.h for the rehash.  Integer arithmetic only; nothing is written.
 //
-// One bucket is walked as rh_walk (k_rehash.hip) and si_walk_chain (state_image.h) walk it: from the inline header's `head`,
-// the inline entry an ordinary chain node wherever it sits and visited at most once, every other link checked by its owner
-// (the pool's size / the image's overflow section) before anything is read through it, KV_MAX_CHAIN entries at most.  A
-// chain that cannot be walked contributes nothing but ST_BAD, and the caller refuses the whole report.
+// One bucket is walked by state_image.h si_chain_walk, the one walk of the export, the check and the rehash: from the inline
+// header's `head`, the inline entry an ordinary chain node wherever it sits and visited at most once, every other link checked
+// by its owner (the pool's size / the bucket's run of the image's overflow section) before anything is read through it,
+// KV_MAX_CHAIN entries at most.  A chain that cannot be walked contributes nothing but ST_BAD, and the caller refuses the
+// whole report.
 //
 // A report is ST_WORDS 64-bit words, word for word the dint_table_stats of include/dint_abi.h:
 //   buckets            local buckets
@@ -27,7 +28,7 @@
 //                      fullest bucket
 //   chain_hist[17]     buckets by entries in the chain, 0..15, the last bin "16 or more"
 //   rows_hist[33]      buckets by valid slots, 0..31, the last bin "32 or more"
-//   locks_held         non-zero tatp lock bytes / smallbank {num_ex, num_sh} pairs with a non-zero word (k_rehash_count's)
+//   locks_held         non-zero tatp lock bytes / smallbank {num_ex, num_sh} pairs with a non-zero word (state_image.h si_locks_held)
 //   pool_cap, pool_top the table's control words (not part of an image: 0 there)
 #pragma once
 #include <stddef.h>
@@ -62,18 +63,13 @@ struct st_bucket {
 SI_HD static inline uint32_t st_chain_bin(uint32_t entries) { return entries < ST_CHAIN_BINS - 1u ? entries : ST_CHAIN_BINS - 1u; }
 SI_HD static inline uint32_t st_rows_bin(uint32_t rows) { return rows < ST_ROWS_BINS - 1u ? rows : ST_ROWS_BINS - 1u; }
 SI_HD static inline bool st_slot_valid(uint32_t validw, uint32_t s) { return (validw >> (8 * s)) & 0xFFu; }
-// lock words held by one bucket: the four lock bytes of a tatp inline header / the eight counter words of a smallbank one
-SI_HD static inline uint32_t st_locks_tatp(uint32_t lockw) { return si_valid_count(lockw); }
-SI_HD static inline uint32_t st_locks_smallbank(const uint32_t c[8]) {
-  return ((c[0] | c[1]) != 0) + ((c[2] | c[3]) != 0) + ((c[4] | c[5]) != 0) + ((c[6] | c[7]) != 0);
-}
 // is (chain, id) a better "longest chain" than (best, best_id)?  longer, or as long at a lower id
 SI_HD static inline bool st_longer(uint64_t chain, uint64_t id, uint64_t best, uint64_t best_id) {
   return chain > best || (chain == best && id < best_id);
 }
 
-// A: uint32_t head(); bool link_ok(link) for a link >= 2; void links(link, validw, next) and void keys(link, k[4]) for link 1
-// or an accepted link >= 2.
+// A: si_chain_walk's accessor -- bool link_ok(link) for a link >= 2; void links(link, validw, next) for link 1 or an accepted
+// link >= 2 -- with uint32_t head() and, for such a link, void keys(link, k[4]).
 //
 // the valid slots of the chain whose key an earlier valid slot holds.  Only called for a chain the walk below has found to
 // end within ST_DUP_MAX_CHAIN entries; it re-walks instead of keeping the chain's keys (no array indexed at run time), and
@@ -121,25 +117,16 @@ template <class A>
 SI_HD static inline st_bucket st_bucket_walk(const A &a) {
   st_bucket r = {0, 0, 0, 0, 0, 0, 0, 0, 1};
   const uint32_t head = a.head();
-  uint32_t link = head;
-  for (uint32_t steps = 0; link != KV_NULL; steps++) {
-    bool ok = steps < KV_MAX_CHAIN;
-    if (ok && link == KV_INLINE) ok = !r.linked;
-    else if (ok) ok = a.link_ok(link);
-    if (!ok) {
-      r = st_bucket{0, 0, 0, 0, 0, 0, 0, 0, 0};
-      return r;
-    }
+  const bool ok = si_chain_walk(head, a, [&](uint32_t pos, uint32_t link, uint32_t validw) {
     if (link == KV_INLINE) r.linked = 1;
     else r.overflow++;
-    uint32_t validw, next;
-    a.links(link, validw, next);
     const uint32_t c = si_valid_count(validw);
     r.rows += c;
-    r.hit += c * (steps + 1u);
+    r.hit += c * (pos + 1u);
     r.entries++;
-    link = next;
-  }
+    return true;
+  });
+  if (!ok) return st_bucket{0, 0, 0, 0, 0, 0, 0, 0, 0};
   r.first = head == KV_INLINE;
   if (r.rows > 1) {  // (a key cannot repeat in a bucket of one row: no key vector is loaded there)
     if (r.entries > ST_DUP_MAX_CHAIN) r.unchecked = 1;

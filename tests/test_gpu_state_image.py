@@ -270,6 +270,55 @@ def test_tatp_twenty_thousand_subscribers_one_to_eight():
     assert _digest_sum(D) == U.state_digest()
 
 
+# ---------------------------------------------------------------------------------------------- 7b. more workgroups than scan threads
+def _by_key(dump):
+    o = np.argsort(dump[0], kind="stable")
+    return tuple(x[o] for x in dump)
+
+
+def test_store_of_more_than_1024_workgroups_export_import_and_rehash():
+    """270,000 buckets = 1,055 workgroups of 256: a thread of the one-workgroup scan of the workgroups' counts (export, the
+    import's check, the rehash) owns two counts.  About 300 chained buckets in workgroups of either parity up to the last
+    one, so a dropped second count shifts the `first` of every later bucket's run."""
+    kw = dict(n_rows=60_000, pool_entries=4096)
+    src = _engine(W.STORE, **kw)
+    hs = src.hash_size(0)
+    assert hs == 270_000 and -(-hs // 256) == 1055
+    cand = tracegen.store_key(7_000_000_000 + np.arange(1_500_000), 1, 0)
+    b = np_bucket(cand, hs).astype(np.int64)
+    chained = cand[(b % 900 == 899) | (b == hs - 1)]  # every candidate of 301 buckets: 5.5 on average
+    keys = np.unique(np.concatenate([cand[:3000], chained]))
+    np.random.default_rng(5).shuffle(keys)
+    vals = ((keys[:, None] >> np.uint64(2)) + np.arange(40, dtype=np.uint64)[None, :] * np.uint64(3)).astype("u1")
+    src.load_rows(0, keys, np.arange(len(keys), dtype="<u4"), vals)
+    assert src.stats()["pool_exhausted"] == 0
+    want, digest = _by_key(src.dump_rows(0)), src.state_digest()
+    assert len(want[0]) == len(keys) and digest[0]["rows"] == len(keys)
+    # export (0, 1) -> (0, 1)
+    buf, n, st = src.state_export(0, 1)
+    assert st["buckets"] == hs and st["rows"] == len(keys) and 200 < st["overflow_entries"] < 4096
+    img = buf[:n].cpu().numpy()
+    assert _lib.load().dint_state_image_check_host(img.ctypes.data, n) == 0
+    off, n_b, n_ovf = (struct.unpack_from("<Q", img, 64 + k)[0] for k in (32, 8, 16))
+    d = np.frombuffer(img, np.dtype([("id", "<u8"), ("first", "<u4"), ("count", "<u4")]), n_b, off)
+    wg = np.nonzero(d["count"])[0] // 256
+    assert n_b == hs and (wg % 2 == 0).any() and (wg % 2 == 1).any() and wg.max() == 1054  # or the test is void
+    count = d["count"].astype(np.int64)
+    assert count.sum() == n_ovf == st["overflow_entries"]
+    assert (d["first"] == np.cumsum(count) - count).all()
+    # ... imported into a blank twin
+    twin = _engine(W.STORE, **kw)
+    assert twin.state_import(buf, n)["rows"] == len(keys)
+    assert twin.state_digest() == digest and same_dump(_by_key(twin.dump_rows(0)), want)
+    # rehashed into a blank engine of the same n_rows
+    dst = _engine(W.STORE, **kw)
+    rs = dst.state_rehash([src])
+    assert rs["rows_placed"] == len(keys) and rs["rows_foreign"] == 0
+    assert dst.state_digest() == digest and same_dump(_by_key(dst.dump_rows(0)), want)
+    for e in (src, twin, dst):
+        e.close()
+
+
 # ---------------------------------------------------------------------------------------------- 8. file
 def _small_tatp(flags=0):
     e = _engine(W.TATP, n_rows=300, log_entries=1 << 16, flags=flags)

@@ -28,9 +28,14 @@ SYMBOLS = [
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
     "dint_log_drain_device", "dint_log_apply_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
     "dint_state_export", "dint_state_import", "dint_state_rehash", "dint_state_stats",
+    "dint_state_verify",
 ]
 #: dint_state_rehash flags
 REHASH_DROP_LOCKS = 1
+#: dint_state_verify flags
+VERIFY_RECLAIM = 1
+#: bytes of a table's control block in a TablesView (include/dint_driver.h DINT_VIEW_CTL_BYTES)
+VIEW_CTL_BYTES = 1600
 
 
 class RouteItem(C.Structure):
@@ -106,6 +111,29 @@ class TableStats(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: (list(getattr(self, k)) if k.endswith("_hist") else int(getattr(self, k))) for k, _ in self._fields_ if k != "reserved"}
+
+
+class TableVerify(C.Structure):
+    """dint_table_verify (include/dint_abi.h)"""
+    _fields_ = [(k, C.c_uint64) for k in (
+        "pool_cap", "pool_top", "rows", "linked", "free_entries", "pending_entries", "unaccounted", "longest_list", "bad_chains",
+        "cross_linked", "linked_beyond_top", "list_bad_links", "stray_valid_entries", "stray_rows", "misplaced_rows", "odd_valid_bytes",
+        "reclaimed", "stray_rows_cleared")] + [("reserved", C.c_uint64 * 14)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class TableView(C.Structure):
+    """dint_table_view (include/dint_driver.h)"""
+    _fields_ = [("entries", C.c_void_p), ("n_local", C.c_uint64), ("hash_size", C.c_uint64), ("pool_cap", C.c_uint32),
+                ("stride", C.c_uint32), ("val_size", C.c_uint32), ("reserved", C.c_uint32), ("pool_next", C.c_void_p), ("ctl", C.c_void_p)]
+
+
+class TablesView(C.Structure):
+    """dint_tables_view (include/dint_driver.h)"""
+    _fields_ = [("workload", C.c_uint32), ("n_tables", C.c_uint32), ("shard_index", C.c_uint32), ("shard_count", C.c_uint32),
+                ("table", TableView * 5)]
 
 
 class DintError(RuntimeError):
@@ -192,6 +220,7 @@ def load() -> C.CDLL:
         "dint_state_import": (C.c_int, [vp, vp, u64, C.POINTER(ImageStats), vp]),
         "dint_state_rehash": (C.c_int, [vp, C.POINTER(vp), u32, u32, C.POINTER(RehashStats), vp]),
         "dint_state_stats": (C.c_int, [vp, C.POINTER(TableStats), u32, vp]),
+        "dint_state_verify": (C.c_int, [vp, C.POINTER(TableVerify), u32, u32, vp]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
         # ... and the state sync's rules (csrc/state_sync.h) over dumped rows
@@ -202,6 +231,9 @@ def load() -> C.CDLL:
         "dint_state_image_check_host": (C.c_int, [vp, u64]),
         # ... and the table report's rule (csrc/state_stats.h) over an image in host memory
         "dint_state_stats_image_host": (C.c_int, [vp, u64, C.POINTER(TableStats), u32]),
+        # ... and the table verify's rule (csrc/state_verify.h) over tables the caller describes, in host / in device memory
+        "dint_state_verify_view_host": (C.c_int, [C.POINTER(TablesView), C.POINTER(TableVerify), u32, u32]),
+        "dint_state_verify_view": (C.c_int, [i32, C.POINTER(TablesView), C.POINTER(TableVerify), u32, u32, vp]),
         # ... and the rehash's layout rule (csrc/state_rehash.h) over keys in source order
         "dint_state_rehash_place_host": (i64, [vp, u64, u64, u32, u32, vp, vp, vp]),
     }

@@ -156,6 +156,34 @@ struct dint_stats_scratch {
 // table t's report (state_stats.h words; not yet st_report_finish'ed) into s.out[DINT_STATE_STATS_WORDS t ..]
 void dint_launch_state_stats(const dint_kv &kv, dint_stats_scratch s, hipStream_t st);
 
+// ---- table verify (k_verify.hip; state_verify.h): the census of chains, lists and pool, and the reclaim of leaked entries ------
+#define DINT_STATE_VERIFY_GRID 2048u   // workgroups per table and stage at most; they stride over the buckets / the pool
+#define DINT_STATE_VERIFY_WORDS 32u    // = SV_WORDS = sizeof(dint_table_verify) / 8
+#define DINT_STATE_VERIFY_PARTS (2u * DINT_STATE_VERIFY_GRID + 1u)  // partial reports of one table: chain stage, the lists, pool stage
+struct dint_verify_scratch {
+  uint32_t *owner;            // [owner_n] the owner words of every table's pool, table after table (cleared by every call)
+  uint64_t owner_n;
+  unsigned long long *part;   // [DINT_KV_MAX_TABLES][DINT_STATE_VERIFY_PARTS][DINT_STATE_VERIFY_WORDS]
+  unsigned long long *out;    // [DINT_KV_MAX_TABLES][DINT_STATE_VERIFY_WORDS] the tables' reports, then one word the scans' totals go to
+  // reclaim only (allocated by the first call that asks for it):
+  uint32_t *leaked;           // [owner_n] per table the unaccounted entries ascending
+  uint32_t *blk_cnt;          // [blk_n] unaccounted entries per 256 pool entries, table after table
+  uint64_t *blk_off;          // [blk_n] ... their exclusive scan, per table
+  uint64_t blk_n;
+  unsigned long long *heads;  // [DINT_KV_MAX_TABLES][KV_NLISTS] the free lists' head words as they were before the reclaim
+};
+// tables of kv that the census cannot take (a table of 2^32 - 256 local buckets or more): DINT_EINVAL, else 0
+int dint_verify_alloc(const dint_kv &kv, dint_verify_scratch &s, uint32_t flags);
+void dint_verify_free(dint_verify_scratch &s);
+// table t's words (state_verify.h; not yet sv_report_finish'ed) into s.out[DINT_STATE_VERIFY_WORDS t ..]; with DINT_VERIFY_RECLAIM
+// the unaccounted entries are back on the free lists afterwards unless a table's words forbid it.  ev (may be null): four events,
+// recorded before the chain stage, behind it, behind the lists, and behind the pool stage and the sum
+void dint_launch_state_verify(const dint_kv &kv, dint_verify_scratch s, uint32_t flags, hipStream_t st, hipEvent_t *ev = nullptr);
+// ... then the one synchronisation: out[t] finished for every table.  Returns 0, DINT_EHIP, or DINT_ESTATE for a refused reclaim;
+// *reclaimed = the entries that went back over all tables
+int dint_verify_collect(const dint_kv &kv, dint_verify_scratch s, uint32_t flags, hipStream_t st, struct dint_table_verify *out,
+                        uint64_t *reclaimed);
+
 // ---- state image (k_image.hip; state_image.h): the tables written out for another shard layout and read back --------
 struct dint_image_scratch {
   unsigned long long *words;  // [DINT_IMAGE_WORDS] device words: [2 t] table t's overflow entries, [2 t + 1] its valid slots,

@@ -136,6 +136,9 @@ struct dint_engine {
   dint_state_scratch state{};
   // table report (dint_state_stats): the workgroups' partial reports and the tables' reports, allocated on the first call
   dint_stats_scratch tstats{};
+  // table verify (dint_state_verify): the owner words, partial reports and reclaim arrays, allocated on the first call and kept
+  dint_verify_scratch tverify{};
+  hipEvent_t ev_verify[4] = {};  // with dint_timing_enable: before the chain stage, behind it, behind the lists, behind pool stage and sum
   // state image (dint_state_export / dint_state_import): scratch, grown on demand; `blank` = created or reset and since then
   // nothing but imports (what dint_state_import asks of its destination); the (source index, source count) pieces imported
   dint_image_scratch image{};
@@ -921,11 +924,14 @@ void dint_engine_destroy(dint_engine_t *e) {
   state_free(e);
   hipFree(e->tstats.part); hipFree(e->tstats.out);
   e->tstats = dint_stats_scratch{};
+  dint_verify_free(e->tverify);
   image_free(e);
   rehash_free(e);
   for (hipEvent_t ev : e->ev_replay)
     if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : e->ev_rehash)
+    if (ev) hipEventDestroy(ev);
+  for (hipEvent_t ev : e->ev_verify)
     if (ev) hipEventDestroy(ev);
   hipFree(e->d_lock_tbl);
   hipFree(e->log.ring);
@@ -1574,6 +1580,36 @@ int dint_state_stats(dint_engine_t *e, dint_table_stats *out, uint32_t cap_table
                   KV_MAX_CHAIN);
   memcpy(out, h, (size_t)e->kv.n_tables * sizeof(dint_table_stats));
   return (int)e->kv.n_tables;
+}
+
+int dint_state_verify(dint_engine_t *e, dint_table_verify *out, uint32_t cap_tables, uint32_t flags, void *stream) {
+  if (!e || !out) return fail(DINT_EINVAL, "null argument");
+  if (flags & ~DINT_VERIFY_RECLAIM) return fail(DINT_EINVAL, "unknown flags %#x", flags);
+  if (int rc = state_check(e, true)) return rc;
+  if (cap_tables < e->kv.n_tables) return fail(DINT_EINVAL, "%u tables, room for %u", e->kv.n_tables, cap_tables);
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = dint_verify_alloc(e->kv, e->tverify, flags)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  const bool timed = e->timer.on;  // stage times: a diagnostic, in out[0].reserved[11..13]
+  if (timed)
+    for (hipEvent_t &ev : e->ev_verify)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  dint_launch_state_verify(e->kv, e->tverify, flags, st, timed ? e->ev_verify : nullptr);
+  if (int rc = state_launched()) return rc;
+  if (int rc = mark_stream(e, st)) return rc;
+  uint64_t reclaimed = 0;
+  const int rc = dint_verify_collect(e->kv, e->tverify, flags, st, out, &reclaimed);  // (the one synchronisation of the call)
+  if (reclaimed) e->blank = false;
+  if (timed && rc != DINT_EHIP)
+    for (int k = 0; k < 3; k++) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, e->ev_verify[k], e->ev_verify[k + 1]));
+      out[0].reserved[11 + k] = (uint64_t)(ms * 1e6);
+    }
+  return rc ? rc : (int)e->kv.n_tables;
 }
 
 int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uint64_t cap, dint_diff_stats *out, void *stream) {

@@ -1,5 +1,6 @@
-// state_dev.h -- device-side building blocks of the state kernels, the four units that read a server's tables where they lie:
-// k_state.hip (digest / diff / repair), k_image.hip (export / import), k_rehash.hip and k_stats.hip (the table report).  None
+// state_dev.h -- device-side building blocks of the state kernels, the five units that read a server's tables where they lie:
+// k_state.hip (digest / diff / repair), k_image.hip (export / import), k_rehash.hip, k_stats.hip (the table report) and
+// k_verify.hip (the census of chains, lists and pool).  None
 // of it is on a request's path, and no other unit includes it.  wave_excl_scan_u32 is dint_device.h's; the rules that host and
 // device share (the chain walk among them) are state_image.h's.
 #pragma once

@@ -292,6 +292,27 @@ class Engine:
         n = _lib.check(self._L.dint_state_stats(self._h, s, 5, stream))
         return [s[t].as_dict() for t in range(n)]
 
+    # ---- table verify (dint_state_verify) ------------------------------------------------------------------
+    def state_verify(self, stream: int = 0, reclaim: bool = False) -> list:
+        """dint_state_verify: per table a dict of the fields of dint_table_verify (include/dint_abi.h; csrc/state_verify.h is
+        the rule) -- the exact census of chains, free lists, pend lists and pool (rows, linked, free_entries, pending_entries,
+        unaccounted, longest_list) and the violations counted (bad_chains, cross_linked, linked_beyond_top, list_bad_links,
+        stray_valid_entries, stray_rows, misplaced_rows, odd_valid_bytes).  Violations are the report, not an error.  Nothing
+        is modified, and a blank engine stays blank."""
+        s = (_lib.TableVerify * 5)()
+        rc = self._L.dint_state_verify(self._h, s, 5, _lib.VERIFY_RECLAIM if reclaim else 0, stream)
+        self.last_verify = [s[t].as_dict() for t in range(_N_TABLES.get(self.workload, 0))]
+        self.last_verify_stage_ns = dict(zip(("chains", "lists", "pool"), list(s[0].reserved)[11:14]))  # with timing_enable on
+        n = _lib.check(rc)
+        return self.last_verify[:n]
+
+    def state_reclaim(self, stream: int = 0) -> list:
+        """dint_state_verify with DINT_VERIFY_RECLAIM: the census, then every table's unaccounted (leaked) pool entries back on
+        its free lists; `reclaimed` says how many.  Raises DintError (DINT_ESTATE) with not a byte written when a table has a
+        bad chain, a cross-linked entry, an entry linked beyond the pool's top or a bad list link; `last_verify` holds the
+        reports also then."""
+        return self.state_verify(stream, reclaim=True)
+
     def stats(self) -> dict:
         s = _lib.Stats()
         _lib.check(self._L.dint_get_stats(self._h, C.byref(s)))

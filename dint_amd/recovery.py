@@ -30,6 +30,10 @@ sources held them, so every key's visible row stays its visible row.  Lock words
 WHEN to do that is what `table_stats` / `rehash_advice` answer: the tables' occupancy and chain shape, computed where they lie
 (dint_state_stats; csrc/k_stats.hip), and the small policy on top of it.  `check_tables` lays the chain walk's row count
 beside the digest's flat one.
+
+All of it assumes structurally sound tables.  `verify_tables` checks that on a shard set (dint_state_verify;
+csrc/k_verify.hip): the census of chains, free lists, pend lists and pool added up, `ok` / `clean`, and on request the leaked
+pool entries put back on the free lists.
 """
 from __future__ import annotations
 
@@ -238,6 +242,30 @@ def check_tables(engine) -> dict:
     st, dg = engine.state_stats(), engine.state_digest()
     tables = [dict(s, digest_rows=d["rows"]) for s, d in zip(st, dg)]
     return {"ok": all(t["rows"] == t["digest_rows"] for t in tables), "tables": tables}
+
+
+#: the counts of a verify report that say "this table is damaged" (Engine.state_verify; csrc/state_verify.h)
+VERIFY_VIOLATIONS = ("bad_chains", "cross_linked", "linked_beyond_top", "list_bad_links", "stray_valid_entries", "stray_rows",
+                     "misplaced_rows", "odd_valid_bytes")
+
+
+def verify_tables(engines, reclaim: bool = False) -> dict:
+    """Engine.state_verify (reclaim=True: Engine.state_reclaim) of every engine of a set -- a shard set, or any engines of one
+    workload -- and the reports added up per table: every count adds, longest_list takes the maximum.  Returns {"ok": every
+    violation count of every table is 0, "clean": ok and nothing unaccounted (before a reclaim: the census is taken first),
+    "tables": the sums per table, "engines": the reports per engine}.  A refused reclaim raises DintError like the engine call."""
+    per = [e.state_reclaim() if reclaim else e.state_verify() for e in engines]
+    tables = None
+    for rep in per:
+        if tables is None:
+            tables = [dict(x) for x in rep]
+            continue
+        for x, y in zip(tables, rep):
+            for k in x:
+                x[k] = max(x[k], y[k]) if k == "longest_list" else x[k] + y[k]
+    tables = tables or []
+    ok = all(t[k] == 0 for t in tables for k in VERIFY_VIOLATIONS)
+    return {"ok": ok, "clean": ok and all(t["unaccounted"] == 0 for t in tables), "tables": tables, "engines": per}
 
 
 def hash_sizes(workload, n_rows: int) -> list:

@@ -452,6 +452,44 @@ typedef struct dint_table_stats {
  * dint_submit_device_ahead pending (DINT_ESTATE); a chain that does not end within 4096 entries, visits its inline entry twice
  * or leaves the pool (DINT_ESTATE; dint_last_error names the table).  The caller keeps the engine quiet for the duration. */
 int dint_state_stats(dint_engine_t *e, dint_table_stats *out, uint32_t cap_tables, void *stream);
+/* ---- table verify (v5, additive): are an engine's tables and overflow pool structurally sound? ---------------------------
+ * Every other state call assumes they are.  This one checks, where the tables lie: an exact census of every chain, every free
+ * list and every pend list of every table, each pool entry claimed by whatever reaches it first, and the violations counted
+ * (dint_amd/csrc/state_verify.h is the rule).  Violations are not an error: they are the report.  While bad_chains,
+ * cross_linked and list_bad_links are 0,  linked + free_entries + pending_entries - linked_beyond_top + unaccounted ==
+ * min(pool_top, pool_cap);  always stray_rows >= stray_valid_entries. */
+#define DINT_VERIFY_RECLAIM 1u /* dint_state_verify flags: put the unaccounted pool entries back on the free lists */
+typedef struct dint_table_verify {
+  uint64_t pool_cap, pool_top;  /* the overflow pool: entries it has / handed out so far (raw, also above pool_cap) */
+  uint64_t rows;                /* valid slots reached by the chain walks */
+  uint64_t linked;              /* distinct pool entries linked into chains */
+  uint64_t free_entries;        /* ... on the 64 free lists */
+  uint64_t pending_entries;     /* ... on the two sets of 64 pend lists */
+  uint64_t unaccounted;         /* ... below pool_top that no chain and no list reaches: leaked */
+  uint64_t longest_list;        /* entries of the longest free or pend list */
+  uint64_t bad_chains;          /* chains that do not end within 4096 entries, visit their inline entry twice or leave the pool */
+  uint64_t cross_linked;        /* times a chain or list met an entry another chain or list (or that list itself) holds */
+  uint64_t linked_beyond_top;   /* pool entries at or above pool_top that a chain or a list reaches */
+  uint64_t list_bad_links;      /* lists that end in a link of 1 or beyond the pool */
+  uint64_t stray_valid_entries; /* entries outside every chain with a valid byte set (a flat scan counts their slots) */
+  uint64_t stray_rows;          /* ... the valid slots they hold */
+  uint64_t misplaced_rows;      /* valid slots whose key hashes to another bucket or shard: no request finds them */
+  uint64_t odd_valid_bytes;     /* valid bytes that are neither 0 nor 1 */
+  uint64_t reclaimed;           /* DINT_VERIFY_RECLAIM: the unaccounted entries put back on the free lists */
+  uint64_t stray_rows_cleared;  /* ... and the valid slots their headers held */
+  uint64_t reserved[14];        /* out[0].reserved[11..13], with dint_timing_enable: nanoseconds of the chain stage, the list stage, the pool stage
+                                   and sum, all tables, between events */
+} dint_table_verify;
+/* (v5, additive) out[t] for every table t of the workload (1 / 5 / 2); returns that number (cap_tables smaller: DINT_EINVAL).
+ * Synchronous like dint_state_stats: orders itself behind the engine's pending work on `stream` (NULL = the engine's own), one
+ * host synchronisation for all tables.  flags = 0: read-only -- nothing of the engine changes and a blank engine stays blank.
+ * DINT_VERIFY_RECLAIM: when bad_chains, cross_linked, linked_beyond_top and list_bad_links are 0 in every table, each table's
+ * unaccounted entries go back to its free lists in ascending order, entry r to list r % 64, their {validw, next} zeroed; the
+ * report is the census BEFORE the repair plus `reclaimed`.  With one of those violations in any table not a byte is written
+ * and the call returns DINT_ESTATE after filling `out`.  The engine stops being blank only if something was reclaimed.  Refused: a
+ * lock_fasst / lock_2pl / log engine, a batch announced by dint_submit_device_ahead pending (DINT_ESTATE).  No content of the
+ * tables makes the kernels read or write outside them or loop without bound.  The caller keeps the engine quiet meanwhile. */
+int dint_state_verify(dint_engine_t *e, dint_table_verify *out, uint32_t cap_tables, uint32_t flags, void *stream);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

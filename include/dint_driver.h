@@ -231,6 +231,34 @@ int dint_state_stats_image_host(const void *image, uint64_t bytes, struct dint_t
 int64_t dint_state_rehash_place_host(const uint64_t *keys, uint64_t n, uint64_t hash_size, uint32_t shard_index, uint32_t shard_count,
                                      uint64_t *bucket_out, uint32_t *link_out, uint32_t *slot_out);
 
+/* ---- table verify: the rule over caller-provided memory (dint_amd/csrc/state_verify.h) ------------------------------------
+ * dint_state_verify (include/dint_abi.h) over tables the CALLER describes: what tests and tools use to show the rule a damaged
+ * table without a poke into a live engine.  Per table: entries = n_local inline entries followed by pool_cap overflow entries
+ * of `stride` bytes (dint_amd/csrc/dint_kv_core.h), hash_size = the table's GLOBAL bucket count (n_local = ceil(hash_size /
+ * shard_count)), pool_next[pool_cap], and ctl = DINT_VIEW_CTL_BYTES in the engine's layout: u32 pool_top at 0, u64
+ * free_head[64] at 64, u64 pend_head[2][64] behind it.  Both forms check the view before anything else -- workload (store /
+ * tatp / smallbank) and table count, stride and value size against the workload's shape, shard_index < shard_count, n_local
+ * against hash_size and below 2^32 - 256, pool_cap <= 2^32 - 16, pointers non-null and aligned (entries 16, ctl 8, pool_next
+ * 4 bytes) -- and answer DINT_EINVAL to one that fails.  out, cap_tables, flags and the return value are dint_state_verify's.
+ * dint_state_verify_view_host: host pointers, no device call.  dint_state_verify_view: device pointers on `device`; the same
+ * launchers as the engine call, scratch allocated and freed by the call, one synchronisation of `stream` (NULL: the null stream). */
+#define DINT_VIEW_CTL_BYTES 1600u
+typedef struct dint_table_view {
+  void *entries;
+  uint64_t n_local, hash_size;
+  uint32_t pool_cap, stride, val_size, reserved;
+  uint32_t *pool_next;
+  void *ctl;
+} dint_table_view;
+typedef struct dint_tables_view {
+  uint32_t workload, n_tables, shard_index, shard_count;
+  dint_table_view table[5];
+} dint_tables_view;
+struct dint_table_verify; /* include/dint_abi.h */
+int dint_state_verify_view_host(const dint_tables_view *view, struct dint_table_verify *out, uint32_t cap_tables, uint32_t flags);
+int dint_state_verify_view(int32_t device, const dint_tables_view *view, struct dint_table_verify *out, uint32_t cap_tables,
+                           uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ struct kv_dev {
   uint32_t n_tables;
   uint32_t shard_index, shard_count;
   uint32_t same_key;  // tatp, DINT_FLAG_LOCK_SAME_KEY: lock slots remember their owner's key (tatp/ebpf/lock_kern.c)
+  uint32_t pass_ins[DINT_KV_MAX_TABLES];  // LDS copies only (k_kv_dev.h, kv_dev_word): INSERT requests of the pass per table; 2^32 - 1 in memory
 };
 
 // Tuning / test knobs of the kv passes, read from the environment ONCE, when the engine is created (r01-r05 read them with

@@ -376,7 +376,7 @@ int ahead_cancel(dint_engine *e) {
   }
   dint_scratch &s = e->scratch;
   for (int k = 0; k < 2; k++) HIP_TRY(hipMemset(s.kvs.bin_cnt[k], 0, DINT_KV_PMAX * sizeof(uint32_t)));
-  HIP_TRY(hipMemset(s.kvs.ctl[0], 0, 3 * 16 * sizeof(uint32_t)));
+  HIP_TRY(hipMemset(s.kvs.ctl[0], 0, 3 * DINT_KV_CTL_WORDS * sizeof(uint32_t)));
   HIP_TRY(hipMemset(s.kvs.pub[0], 0, 3 * 1024 * sizeof(uint32_t)));
   if (e->log.tail) {  // the tail the cancelled partition published is not the current one
     uint32_t t[4];
@@ -816,7 +816,7 @@ int dint_engine_create(const dint_config *cfg, dint_engine_t **out) {
     TRY(dev_alloc((void **)&e->scratch.big, 2 * (4 + DINT_KV_PMAX) * sizeof(uint32_t)));
     e->scratch.big_next = e->scratch.big + (4 + DINT_KV_PMAX);
     if (is_kv)  // (the three sets of control words and tile counts live in the allocations the lock tables use as two)
-      for (int k = 0; k < 3; k++) { e->scratch.kvs.ctl[k] = e->scratch.big + 16 * k; e->scratch.kvs.pub[k] = e->scratch.blk_pub + 1024 * k; }
+      for (int k = 0; k < 3; k++) { e->scratch.kvs.ctl[k] = e->scratch.big + DINT_KV_CTL_WORDS * k; e->scratch.kvs.pub[k] = e->scratch.blk_pub + 1024 * k; }
     TRY(dev_alloc((void **)&e->scratch.bin_off, DINT_KV_PMAX * sizeof(uint32_t)));
     TRY(hipMemset(e->scratch.bin_off, 0xFF, DINT_KV_PMAX * sizeof(uint32_t)) == hipSuccess ? 0 : fail(DINT_EHIP, "hipMemset"));  // (lock tables, direct big bins: "no region named" between passes)
     TRY(dev_alloc((void **)&e->scratch.ovl, (size_t)e->pass_max * sizeof(uint4) * (is_kv ? 2 : 1), false));
@@ -839,7 +839,7 @@ int dint_engine_create(const dint_config *cfg, dint_engine_t **out) {
     dint_engine_destroy(e);
     return fail(DINT_ENOMEM, "hipHostMalloc");
   }
-  *e->h_pool = 0;
+  e->h_pool[0] = e->h_pool[1] = 0;  // [0] read back with each host chunk (dint_wait), [1] by dint_sync
 
   if (wl == DINT_WL_FASST || wl == DINT_WL_2PL) {
     e->n_slots = cfg->n_slots ? cfg->n_slots : 36000000ull;  // lock_fasst/udp/utils.h:12
@@ -1387,11 +1387,14 @@ int dint_stream_signal(dint_engine_t *e, void *other_stream) {
 int dint_sync(dint_engine_t *e) {
   if (!e) return fail(DINT_EINVAL, "null engine");
   hipStream_t s0, s1, s2;
+  HIP_TRY(hipSetDevice(e->device));
   {
     std::lock_guard<std::mutex> lk(e->mu);  // the copy streams are created lazily by the first host submission
     s0 = e->stream; s1 = e->s_h2d; s2 = e->s_d2h;
+    // kv engines: the overflow-pool counter travels behind the work on the engine's stream, into the word next to the host path's
+    if (e->kv.n_tables)
+      HIP_TRY(hipMemcpyAsync(e->h_pool + 1, &e->scratch.stats->pool_exhausted, sizeof(unsigned long long), hipMemcpyDeviceToHost, s0));
   }
-  HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(s0));
   if (s1 && s1 != s0) HIP_TRY(hipStreamSynchronize(s1));
   if (s2 && s2 != s0) HIP_TRY(hipStreamSynchronize(s2));
@@ -1403,6 +1406,15 @@ int dint_sync(dint_engine_t *e) {
       HIP_TRY(hipEventSynchronize(sl.done));
       slot_deliver(sl);
     }
+  // INSERTs of device submissions (dint_submit_device: no dint_wait ever sees them) that found the pool full are reported here,
+  // once, as dint_wait reports the host path's (pool_seen and h_pool are compared and updated under e->mu, taken above, as there)
+  if (e->kv.n_tables && e->h_pool[1] > e->pool_seen) {
+    const unsigned long long lost = e->h_pool[1] - e->pool_seen;
+    e->pool_seen = e->h_pool[1];
+    if (*e->h_pool < e->h_pool[1]) *e->h_pool = e->h_pool[1];
+    return fail(DINT_ENOMEM, "%llu INSERTs found the overflow-entry pool full (dint_config.pool_entries); "
+                             "they were answered with a reject code and stored nothing", lost);
+  }
   return 0;
 }
 
@@ -1686,6 +1698,7 @@ int dint_state_repair(dint_engine_t *e, const void *d_records, uint64_t n, dint_
     // reported here: the host path's own check (dint_wait) must not report these inserts a second time
     e->pool_seen += h[4];
     *e->h_pool += h[4];
+    if (e->h_pool[1] < e->pool_seen) e->h_pool[1] = e->pool_seen;
     return fail(DINT_ENOMEM, "%llu inserts found the overflow-entry pool full (dint_config.pool_entries); the other records were applied", h[4]);
   }
   return 0;
@@ -2045,7 +2058,7 @@ int dint_reset(dint_engine_t *e) {
   e->batches = e->requests = 0;
   e->log_drained = 0;
   e->pool_seen = 0;
-  *e->h_pool = 0;
+  e->h_pool[0] = e->h_pool[1] = 0;
   HIP_TRY(hipDeviceSynchronize());
   return 0;
 }
@@ -2089,7 +2102,7 @@ int dint_restore(dint_engine_t *e) {
     HIP_TRY(hipMemcpy(e->regions[i].first, e->snap[i], e->regions[i].second, hipMemcpyDeviceToDevice));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(e->h_pool, &e->scratch.stats->pool_exhausted, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  e->pool_seen = *e->h_pool;
+  e->pool_seen = e->h_pool[1] = *e->h_pool;
   e->log_drained = e->snap_log_drained;  // the drain cursor belongs to the log's history
   return 0;
 }

@@ -293,6 +293,9 @@ int dint_kv_create(dint_kv *kv, uint32_t workload, uint64_t n_rows, dint_shard s
   kv->h.n_tables = kv->n_tables;
   kv->h.shard_index = shard.index;
   kv->h.shard_count = count;
+  // (in memory: "always low" -- a kernel that handed kv_pool_low these descriptors and not a workgroup's LDS copy, which carries
+  // the pass's INSERT counts, would send every inserting run request by request, never acknowledge an INSERT unchecked)
+  for (uint32_t t = 0; t < DINT_KV_MAX_TABLES; t++) kv->h.pass_ins[t] = 0xFFFFFFFFu;
   if (hipMalloc((void **)&kv->d_ctl, DINT_KV_CTL_BYTES * DINT_KV_MAX_TABLES) != hipSuccess) return DINT_ENOMEM;
   hipMemset(kv->d_ctl, 0, DINT_KV_CTL_BYTES * DINT_KV_MAX_TABLES);
   uint64_t gk = 0;

@@ -4,6 +4,7 @@
 // 3,800-line unit that took two minutes to compile; the kernels themselves are unchanged by the split.)
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <utility>
@@ -82,6 +83,18 @@ struct kv_dev_mem {
 __device__ static inline void kv_dev_pend_set(kv_dev &Skv, uint32_t pno) {
   if (threadIdx.x < DINT_KV_MAX_TABLES && (pno & 1u)) Skv.tab[threadIdx.x].pend_head += KV_NLISTS;
 }
+// Word w of the descriptors as a workgroup copies them to LDS.  The words of kv_dev::pass_ins come from the pass's control words
+// instead: the INSERTs this pass holds per table, counted by its partition -- an earlier launch --, what kv_pool_low compares
+// the pool's head-room with.  One load per thread either way, on the round trip of the copy.  The counts lie 128 bytes behind
+// the words [0 .. 7) of the set: those are one cache line that the hot-key workers poll and every workgroup bumps with atomics
+// all through the launch, and a load of that line at the start of every workgroup queued behind them (counts at word 8: the
+// tatp bench stream 3,040 -> 2,700 Mtxn/s; on a line of their own: as without the load).
+#define KV_CTL_INS 32u  // control words [32 .. 32 + DINT_KV_MAX_TABLES): INSERT requests of the pass per table (dint_kv_sets::ctl)
+static_assert(KV_CTL_INS + DINT_KV_MAX_TABLES <= DINT_KV_CTL_WORDS && KV_CTL_INS * 4 >= 128, "a set of control words is DINT_KV_CTL_WORDS; the counts on a line of their own");
+__device__ static inline uint32_t kv_dev_word(const kv_dev *kv, const uint32_t *ctl, uint32_t w) {
+  constexpr uint32_t at = (uint32_t)(offsetof(kv_dev, pass_ins) / 4);
+  return w >= at && w < at + DINT_KV_MAX_TABLES ? ctl[KV_CTL_INS + w - at] : ((const uint32_t *)kv)[w];
+}
 // What a resolve workgroup hands to the hot-key workers of the SAME launch (k_kv_pass): the 8-byte records of a big sub, its work
 // items and their "listed" tags.  The two sit on different XCDs as a rule, whose L2s are not coherent: agent-scope accesses
 // (write-through / L2-bypassing on gfx950) instead of a release that would write a whole L2 back.
@@ -148,6 +161,12 @@ __device__ static inline kv_reqinfo kv_read_request(const uint8_t *m, bool live,
     if (r.cls) r.key = ld_u64(m + F::KEY);
   }
   return r;
+}
+
+// the wire INSERTs (store INSERT, tatp INSERT_PRIM / INSERT_BCK): the requests that may take an entry from the overflow pool
+template <int WL>
+__device__ static inline bool kv_insert_op(uint32_t type) {
+  return WL == DINT_WL_STORE ? type == 2 : WL == DINT_WL_TATP ? (type == 18 || type == 19) : false;
 }
 
 // ---- one pass of one engine, as the kernels see it -------------------------------------------------------------
@@ -222,6 +241,7 @@ struct kv_part_lds {
   uint32_t Hc[DINT_KV_CMAX];  // records of this tile per coarse bin; then the position of the tile's first one
   uint32_t Sov[2];            // overflow records of the tile; their place in the pass's list
   uint32_t Stile;
+  uint32_t Sins[DINT_KV_MAX_TABLES];  // INSERT requests of the tile per table (kv_pool_low)
   uint32_t Swl[TB / 64 * RPT], Swp[TB / 64];
 };
 template <int WL, int RPT, uint32_t TB = KV_TB>
@@ -237,6 +257,7 @@ __device__ __forceinline__ static void kv_part_body(const kv_pass_args &A, kv_pa
   // tiles are handed out in start order (a ticket, not blockIdx), so the tiles before mine belong to workgroups that
   // are already running: what the log-position look-back below waits for
   if (t == 0) { Stile = atomicAdd(&A.big[2], 1u); Sov[0] = 0; }
+  if (t < DINT_KV_MAX_TABLES) S.Sins[t] = 0;
   for (uint32_t k = t; k < C; k += TB) Hc[k] = 0;
   __syncthreads();
   const uint32_t tile = Stile;
@@ -307,6 +328,7 @@ __device__ __forceinline__ static void kv_part_body(const kv_pass_args &A, kv_pa
         const uint32_t gq = kv_cut_div(kv->gk_base[r[j].table] + local, A.cut, &coarse[j]);
         meta[j] = kv_rec(gq, idx[j], kv_pay(r[j].type, q, (uint32_t)(h >> 40) & 511u), A.cut);  // the table is implied by the group key
         mypos[j] = atomicAdd(&Hc[coarse[j]], 1u);
+        if (kv_insert_op<WL>(r[j].type)) atomicAdd(&S.Sins[r[j].table], 1u);
       }
     }
   }
@@ -315,6 +337,7 @@ __device__ __forceinline__ static void kv_part_body(const kv_pass_args &A, kv_pa
     const uint32_t cnt = Hc[c];
     if (cnt) Hc[c] = atomicAdd(&A.bin_cnt[c], cnt);
   }
+  if (WL != DINT_WL_SMALLBANK && t < DINT_KV_MAX_TABLES && S.Sins[t]) atomicAdd(&A.big[KV_CTL_INS + t], S.Sins[t]);
   __syncthreads();
   uint32_t orank[RPT];
   bool over[RPT];
@@ -425,13 +448,19 @@ __device__ static inline void kv_stamp_real(uint64_t *tr, uint32_t k) {
   if (tr && lane_id() == 0) tr[k] = __builtin_amdgcn_s_memrealtime();
 }
 
-// The overflow-entry pool is nearly used up: a bucket run that inserts goes request by request (kv_do_request answers
-// an INSERT that finds the pool full with the reject code and leaves its lock byte alone; a closed form has written
-// its replies before the one physical insert at the write-back can fail -- ADVICE r02).  The margin covers the
-// inserts other waves have in flight; recycled entries are ignored, which only makes the answer more careful.
-#define KV_POOL_MARGIN 4096u
-__device__ static inline uint32_t kv_pool_low(const kv_tab &t) {
-  return __hip_atomic_load(t.pool_top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + KV_POOL_MARGIN >= t.pool_cap;
+// The overflow-entry pool may run out during this pass: a bucket run that inserts goes request by request (kv_do_request
+// answers an INSERT that finds the pool full with the reject code and leaves its lock byte alone; a closed form has written
+// its replies before the one physical insert at the write-back can fail -- ADVICE r02).  No reply says ACK for an INSERT
+// that can fail: the pass's partition counted its INSERTs per table (pass_ins, kv_dev_word), each takes at most one
+// entry, and the bump allocator never moves back -- so with pool_top + pass_ins <= pool_cap NOW, every insert of the pass
+// finds an entry, whenever it is made and however many waves are between this check and their write-back.  (pool_top
+// already holds the entries this pass has taken, recycled entries are ignored, an INSERT into a free slot takes none: all of
+// which only makes the answer more careful.  Until r06 a constant margin of 4,096 entries stood where pass_ins stands: a pass
+// may hold far more inserting leaders than that between check and write-back, and their failed inserts had said ACK.)  The
+// next pass's inserts are not in flight beside this one's: only its partition runs ahead (k_kv_pass).
+__device__ static inline uint32_t kv_pool_low(const kv_dev *kv, uint32_t table) {
+  const kv_tab &t = kv->tab[table];
+  return (uint64_t)__hip_atomic_load(t.pool_top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + kv->pass_ins[table] > t.pool_cap;
 }
 
 // ---- one request against the table ---------------------------------------------------------------------
@@ -722,7 +751,7 @@ __device__ static inline void kv_chunk(uint8_t *rep, bool valid, uint32_t idx, u
     if (WL == DINT_WL_TATP) la0 = (H.lockw >> (8 * q)) & 0xFFu;
     const kv_where w = kv_locate(t, bucket, H, key);
     found = w.found; link = w.link; slot = w.slot; ver0 = w.ver;
-    if (WL != DINT_WL_SMALLBANK && structural) dupf = kv_has_dup(t, bucket, H, key, w) | kv_pool_low(t);
+    if (WL != DINT_WL_SMALLBANK && structural) dupf = kv_has_dup(t, bucket, H, key, w) | kv_pool_low(kv, table);
   }
   found = __shfl(found, hl, 64); link = __shfl(link, hl, 64); slot = __shfl(slot, hl, 64);
   ver0 = __shfl(ver0, hl, 64); la0 = __shfl(la0, hl, 64); lb0 = __shfl(lb0, hl, 64);
@@ -1874,7 +1903,7 @@ kv_big_bin(uint8_t *rep, uint32_t n, const kv_cut cut, const kv_dev *kv, uint32_
         if (WL != DINT_WL_SMALLBANK) {
           if (kvb_bit(Mstseg, a)) {  // the segment inserts / deletes
             Crow[t].exists = wh.found; Crow[t].ver = wh.ver; Crow[t].toggles = 0; Crow[t].miss = 0; Crow[t].src = -1;
-            Crow[t].bail = kv_has_dup(tb, bucket, H, key, wh) | kv_pool_low(tb);  // duplicate rows of this key, or hardly an overflow entry left: request by request
+            Crow[t].bail = kv_has_dup(tb, bucket, H, key, wh) | kv_pool_low(kv, table);  // duplicate rows of this key, or hardly an overflow entry left: request by request
             Sany = 1;
           }
         }
@@ -2641,7 +2670,7 @@ __device__ __forceinline__ static void kv_resolve_role(const kv_pass_args &A, ui
   const uint4 *__restrict__ recs = A.kbins + (size_t)b * A.cap;
   const uint4 r0 = t < A.cap ? recs[t] : make_uint4(0, 0, 0, 0);
   const uint4 r1 = t + NT < A.cap ? recs[t + NT] : make_uint4(0, 0, 0, 0);
-  const uint32_t kvw = t < sizeof(kv_dev) / 4 ? ((const uint32_t *)A.kv)[t] : 0u;
+  const uint32_t kvw = t < sizeof(kv_dev) / 4 ? kv_dev_word(A.kv, A.big, t) : 0u;
   const uint32_t cnt = A.bin_cnt[b];
   if (t < sizeof(kv_dev) / 4) ((uint32_t *)&Skv)[t] = kvw;
   if (t < KVR_F) {
@@ -2650,7 +2679,7 @@ __device__ __forceinline__ static void kv_resolve_role(const kv_pass_args &A, ui
     L.hist[t] = 0; L.cur[t] = 0; L.cflag[t] = 0;
   }
   if (b == 0) {  // the control words of the pass AFTER NEXT: the next pass's partition may be running beside this workgroup (k_kv_pass)
-    if (t < 16) A.big_z[t] = 0;
+    if (t < 16 || (t >= KV_CTL_INS && t < KV_CTL_INS + DINT_KV_MAX_TABLES)) A.big_z[t] = 0;
     for (uint32_t k = t; k < 1024; k += NT) A.blk_pub_z[k] = 0;
   }
   __syncthreads();
@@ -2827,7 +2856,7 @@ __device__ __forceinline__ static bool kv_group_phases(uint8_t *rep, const kv_cu
   const bool isW = v && (is_set(my_type) || is_ins(my_type) || is_del(my_type)), isR = v && my_type == 0;
   const bool lk = v && kv_lock_op<WL>(my_type), aq = v && WL == DINT_WL_TATP && my_type == 1;
   if (v && !(kv_simple_op<WL>(my_type) || kv_struct_op<WL>(my_type))) H.gbad = 1;
-  if (v && is_ins(my_type) && kv_pool_low(tb)) H.gbad = 1;
+  if (v && is_ins(my_type) && kv_pool_low(kv, table)) H.gbad = 1;
   const uint64_t bw = __ballot(isW);
   if (lane == 0) H.Bw[wave] = bw;
   if (WL == DINT_WL_TATP) {
@@ -3049,7 +3078,7 @@ __device__ __forceinline__ static int kv_solo_item(uint8_t *rep, const kv_cut cu
     }
     uint32_t ex = wh.found, ver = wh.ver, toggles = 0, miss = 0, e = 0;
     int sr = -1;
-    const uint32_t plow = structural ? kv_pool_low(tb) : 0u;
+    const uint32_t plow = structural ? kv_pool_low(kv, table) : 0u;
     uint32_t bail = plow | ((structural && kv_has_dup(tb, bucket, Hd, hkey, wh)) ? 1u : 0u);
     for (uint32_t wv = 0; wv < KVB_W; wv++)
       for (uint64_t mm = H.Bw[wv]; mm; mm &= mm - 1) {
@@ -3561,7 +3590,7 @@ __global__ void __launch_bounds__(KVB_T, WPS) k_kv_late(kv_multi_args M, uint32_
   const uint32_t nq = A.big[5];
   if (blockIdx.x >= nq || dry) return;  // (almost always: nothing was left)
   const uint32_t t = threadIdx.x;
-  if (t < sizeof(kv_dev) / 4) ((uint32_t *)&Skv)[t] = ((const uint32_t *)A.kv)[t];
+  if (t < sizeof(kv_dev) / 4) ((uint32_t *)&Skv)[t] = kv_dev_word(A.kv, A.big, t);
   __syncthreads();
   kv_dev_pend_set(Skv, A.pno);
   __syncthreads();
@@ -3925,7 +3954,7 @@ static_assert(sizeof(kvb_lds) + (KV_HOT_BM ? KV_HOT_BM_W * 10 : 16) + sizeof(kv_
 template <int WL>
 __device__ __forceinline__ static void kv_hot_role(const kv_pass_args &A, kv_dev &Skv, uint8_t *Lraw, uint32_t &Stk, uint32_t bx, uint32_t by) {
   const uint32_t t = threadIdx.x;
-  if (t < sizeof(kv_dev) / 4) ((uint32_t *)&Skv)[t] = ((const uint32_t *)A.kv)[t];
+  if (t < sizeof(kv_dev) / 4) ((uint32_t *)&Skv)[t] = kv_dev_word(A.kv, A.big, t);
   __syncthreads();
   kv_dev_pend_set(Skv, A.pno);  // (the ticket loop below starts with a barrier)
   kv_cut cut2 = A.cut;
@@ -4083,7 +4112,7 @@ __global__ void __launch_bounds__(KVB_T, 1) k_kv_big(kv_multi_args M, uint32_t f
   const uint32_t nq = from_late ? A.big[5] : A.big[3];
   if (blockIdx.x >= nq) return;
   const uint32_t t = threadIdx.x;
-  if (t < sizeof(kv_dev) / 4) ((uint32_t *)&Skv)[t] = ((const uint32_t *)A.kv)[t];
+  if (t < sizeof(kv_dev) / 4) ((uint32_t *)&Skv)[t] = kv_dev_word(A.kv, A.big, t);
   __syncthreads();
   kv_dev_pend_set(Skv, A.pno);
   __syncthreads();

@@ -144,8 +144,9 @@ typedef struct dint_stats {
   uint64_t foreign_requests; /* request whose home shard is not this engine: left untouched */
   uint64_t pool_exhausted; /* INSERTs that found the overflow-entry pool full: nothing is stored; a request resolved on
                               its own is answered REJECT_INSERT (store, 9) / REJECT_COMMIT (tatp, 11 -- the eBPF
-                              flavour's "refused, send again", tatp/ebpf/shard_kern.c:509-514), one folded into a
-                              same-key closed form keeps its ack; dint_wait / dint_submit return DINT_ENOMEM */
+                              flavour's "refused, send again", tatp/ebpf/shard_kern.c:509-514) -- every one: a bucket
+                              run that inserts leaves the closed forms while the pass's INSERTs could use the pool up;
+                              dint_wait / dint_submit / dint_sync return DINT_ENOMEM */
   uint64_t route_overflow; /* requests dint_route_pack could not place (destination slot full): answered by
                               dint_route_unpack with the back-pressure reply of dint_refuse ("not now, send again") */
   uint64_t big_bin_requests; /* kv workloads: requests that were resolved by the big-bin kernel (hot keys) */
@@ -184,7 +185,9 @@ int dint_submit(dint_engine_t *e, const void *reqs, uint32_t n, void *replies);
 typedef uint64_t dint_ticket;
 int dint_submit_async(dint_engine_t *e, const void *reqs, uint32_t n, void *replies, dint_ticket *ticket);
 /* replies of `ticket` (and of every earlier ticket) are complete.  DINT_ENOMEM if INSERTs were refused since the
- * last check (dint_stats.pool_exhausted) -- the replies are valid, rows were not stored. */
+ * last check (dint_stats.pool_exhausted) -- the replies are valid, rows were not stored.  Every refusal is reported once: a
+ * dint_sync between the submission and its dint_wait takes the report, and the dint_wait then returns 0.  Refusals of
+ * dint_submit_device batches on a caller's stream are reported by the first dint_wait / dint_sync after they have run. */
 int dint_wait(dint_engine_t *e, dint_ticket ticket);
 int dint_alloc_pinned(size_t bytes, void **out);
 void dint_free_pinned(void *p);
@@ -215,7 +218,9 @@ int dint_submit_device(dint_engine_t *e, const void *d_reqs, uint32_t n, void *d
 int dint_submit_device_ahead(dint_engine_t *e, const void *d_reqs, uint32_t n, void *d_replies, const void *d_next_reqs,
                              uint32_t next_n, void *d_next_replies, void *stream);
 /* wait for everything enqueued on the engine's own streams; replies of dint_submit_async calls from pageable memory that are
- * still staged in the engine's page-locked buffers reach the caller's buffers here too (as in dint_wait) */
+ * still staged in the engine's page-locked buffers reach the caller's buffers here too (as in dint_wait).  store / tatp:
+ * DINT_ENOMEM if INSERTs -- of dint_submit_device batches on the engine's own stream, which no dint_wait sees -- were refused
+ * since the last check (dint_stats.pool_exhausted); everything is complete and the replies are valid also then. */
 int dint_sync(dint_engine_t *e);
 /* the engine's own stream (a hipStream_t) */
 void *dint_engine_stream(dint_engine_t *e);

@@ -41,6 +41,13 @@ int kvh_insert(kvh *h, uint64_t bucket, uint64_t key, const uint8_t *val, uint32
 int kvh_delete(kvh *h, uint64_t bucket, uint64_t key) { return kv_delete<kv_host_mem>(h->t, bucket, key) ? 0 : 1; }
 void kvh_rotate(kvh *h) { for (uint32_t l = 0; l < KV_NLISTS; l++) kv_pool_rotate<kv_host_mem>(h->t, l); }
 uint32_t kvh_pool_top(kvh *h) { return h->pool_top; }
+// entries on the free lists (set 0: poppable now) / on the pend lists (set 1: poppable after the next rotation)
+uint32_t kvh_listed(kvh *h, int pend) {
+  uint32_t n = 0;
+  for (uint32_t l = 0; l < KV_NLISTS; l++)
+    for (uint32_t cur = (uint32_t)(pend ? h->pend_head[l] : h->free_head[l]); cur != KV_NULL && n <= h->t.pool_cap; cur = h->t.pool_next[cur - 2u]) n++;
+  return n;
+}
 // lock words share the inline entry with the rows: poke them to prove row ops never clobber them
 void kvh_set_lock_bytes(kvh *h, uint64_t bucket, uint32_t v) {
   kv_entry_hdr(h->t, bucket, KV_INLINE)->lockw = v;

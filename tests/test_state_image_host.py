@@ -11,17 +11,13 @@ import pytest
 import tracegen
 from dint_amd import _lib, recovery, wire
 from oracle import oracle as orc
-from shard_double import fasthash_key
+from kvkeys import np_bucket  # noqa: F401  (the GPU tests import it from here)
 
 W = wire.Workload
 EINVAL = -1
 
 
 # ------------------------------------------------------------------------------------------------ numpy reference forms
-def np_bucket(keys, hash_size):
-    return fasthash_key(np.asarray(keys, np.uint64)) % np.uint64(hash_size)
-
-
 def np_select(dump, hash_size, j, H):
     """the rows of a bucket-ordered dump that live on shard j of H: a stable selection"""
     keys, vers, vals = dump

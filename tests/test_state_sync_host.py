@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from dint_amd import _lib, wire
+from kvkeys import np_bucket  # noqa: F401  (other test modules import it from here)
 from oracle import oracle as orc
 
 EINVAL = -1
@@ -55,11 +56,6 @@ def np_digest(table, keys, vers, vals) -> dict:
     h = np_fasthash64(canonical(table, keys, vers, vals))
     return {"rows": len(h), "sum": int(h.sum(dtype=np.uint64)) if len(h) else 0,
             "xr": int(np.bitwise_xor.reduce(h)) if len(h) else 0}
-
-
-def np_bucket(keys, hash_size: int) -> np.ndarray:
-    keys = np.ascontiguousarray(keys, "<u8")
-    return np_fasthash64(keys.view(np.uint8).reshape(-1, 8)) % np.uint64(hash_size)
 
 
 def _visible(keys):

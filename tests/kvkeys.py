@@ -201,3 +201,87 @@ def churn_pool(wl, passes, kind="issue"):
     pool = max(table_needs(wl, o)) // 2
     assert pool >= max(pop) > 0, (pool, pop)
     return pool
+
+
+# ---- keys that share a bucket and the 9 key-hash bits of the kv pass (tests/kv_collide.py builds its traces from these) -------------
+def key_sig(keys, hash_size: int):
+    """(bucket, lock quadrant, key-hash bits) of every key as the kv pass's partition computes them from h = fasthash64(key):
+    h % hash_size, (h % (4 * hash_size)) // hash_size, (h >> 40) & 511"""
+    h = fasthash_key(np.ascontiguousarray(np.atleast_1d(keys), "<u8"))
+    hs = np.uint64(hash_size)
+    return h % hs, (h % (np.uint64(4) * hs)) // hs, (h >> np.uint64(40)) & np.uint64(511)
+
+
+_LIKE, _GROUPS = {}, {}
+
+
+def keys_like(key: int, hash_size: int, n: int, *, same_kh: bool, same_quadrant: bool, seed: int, key_of=None, exclude=()) -> np.ndarray:
+    """n distinct keys other than `key` (and than `exclude`) in key's bucket of hash_size, whose key-hash bits / lock quadrant
+    equal key's or differ from them as asked (same_quadrant=None: either); `key_of` maps the 48-bit candidates to keys of the form a workload wants.
+    Results are kept per argument set: a parametrized test searches once."""
+    memo = (int(key), hash_size, n, same_kh, same_quadrant, seed, key_of, tuple(int(x) for x in exclude))
+    if memo in _LIKE:
+        return _LIKE[memo].copy()
+    b0, q0, k0 = (int(x[0]) for x in key_sig([key], hash_size))
+    rng = np.random.default_rng(seed)
+    out = np.zeros(0, np.uint64)
+    bad = np.array([int(key), *memo[-1]], np.uint64)
+    for _ in range(4000):
+        cand = rng.integers(1, 1 << 48, 1 << 20, dtype=np.uint64)
+        cand = key_of(cand) if key_of else cand
+        b, q, k = key_sig(cand, hash_size)
+        ok = (b == np.uint64(b0)) & ((k == np.uint64(k0)) == same_kh)
+        if same_quadrant is not None:  # (None: any quadrant -- the store has no lock bytes)
+            ok &= (q == np.uint64(q0)) == same_quadrant
+        if ok.any():
+            new = cand[ok]
+            out = np.concatenate([out, new[~np.isin(new, bad) & ~np.isin(new, out)]])
+            out = out[np.sort(np.unique(out, return_index=True)[1])]
+            if len(out) >= n:
+                _LIKE[memo] = out[:n].copy()
+                return out[:n]
+    raise AssertionError("no such keys among 2^32 candidates")
+
+
+def collision_groups(hash_size: int, n_groups: int, per_group: int, seed: int, key_of=None) -> np.ndarray:
+    """(n_groups, per_group) distinct keys: a row shares bucket and key-hash bits, different rows lie in different buckets.
+    A birthday search over the cells (bucket, key hash) of 200,000 candidates, doubled until there are enough."""
+    memo = (hash_size, n_groups, per_group, seed, key_of)
+    if memo in _GROUPS:
+        return _GROUPS[memo].copy()
+    rng = np.random.default_rng(seed)
+    keys = np.zeros(0, np.uint64)
+    draw = 200_000
+    for _ in range(8):
+        cand = rng.integers(1, 1 << 48, draw, dtype=np.uint64)
+        keys = np.unique(np.concatenate([keys, key_of(cand) if key_of else cand]))
+        b, _, k = key_sig(keys, hash_size)
+        cell = b * np.uint64(512) + k
+        o = np.argsort(cell, kind="stable")
+        sc = cell[o]
+        first = np.searchsorted(sc, sc, side="left")
+        rank = np.arange(len(o)) - first
+        heads = first[rank == per_group - 1]  # cells with at least per_group keys
+        _, pick = np.unique(sc[heads] // np.uint64(512), return_index=True)  # one cell per bucket
+        if len(pick) >= n_groups:
+            heads = heads[pick][rng.permutation(len(pick))[:n_groups]]
+            out = keys[o][heads[:, None] + np.arange(per_group)[None, :]]
+            _GROUPS[memo] = out.copy()
+            return out
+        draw *= 2
+    raise AssertionError("not enough candidate keys for the groups")
+
+
+def colliding_pairs(keys, hash_size: int, same_quadrant: bool) -> np.ndarray:
+    """all pairs (a, b), a before b, among `keys` (distinct) that share bucket and key-hash bits and whose lock quadrants are equal or
+    not as asked: the pairs a populated table holds"""
+    keys = np.ascontiguousarray(keys, "<u8")
+    b, q, k = key_sig(keys, hash_size)
+    cell = b * np.uint64(512) + k
+    o = np.argsort(cell, kind="stable")
+    sc, sq, sk = cell[o], q[o], keys[o]
+    out = []
+    for i in np.nonzero(sc[1:] == sc[:-1])[0]:
+        if (sq[i] == sq[i + 1]) == same_quadrant:
+            out.append((int(sk[i]), int(sk[i + 1])))
+    return np.array(out, np.uint64).reshape(-1, 2)

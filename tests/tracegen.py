@@ -82,7 +82,7 @@ def store_random(n, seed=0, n_sub_touch=50, p_set=0.4, p_missing=0.1, p_insert=0
 T = wire.Tatp
 
 
-def tatp_random(n, existing, seed=0, n_sub_touch=40, well_formed=True):
+def tatp_random(n, existing, seed=0, n_sub_touch=40, well_formed=True, pools=None):
     """Random mix of all 13 tatp request types.
 
     `existing` = list of 5 key arrays (rows that exist initially, e.g. from the
@@ -90,12 +90,17 @@ def tatp_random(n, existing, seed=0, n_sub_touch=40, well_formed=True):
     well_formed=True the generator tracks existence so that COMMIT/DELETE only
     hit existing rows and INSERT only missing ones (the cases on which the
     reference udp server does not panic, tatp/udp/kvs.h:91,152).
+    `pools` = five sorted key lists to draw every table's keys from, instead of the rows of
+    `existing` plus the plausible keys of the first n_sub_touch subscribers.
     """
     rng = np.random.default_rng(seed)
     m = np.zeros(n, wire.TATP_MSG)
     live = [set(int(k) for k in ks) for ks in existing]
-    pools = []
+    given, pools = pools, []
     for t in range(5):
+        if given is not None:
+            pools.append([int(k) for k in given[t]])
+            continue
         pool = set(live[t])
         # add plausible missing keys
         for s in range(n_sub_touch):

@@ -28,12 +28,14 @@ SYMBOLS = [
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
     "dint_log_drain_device", "dint_log_apply_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
     "dint_state_export", "dint_state_import", "dint_state_rehash", "dint_state_stats",
-    "dint_state_verify",
+    "dint_state_verify", "dint_state_compact",
 ]
 #: dint_state_rehash flags
 REHASH_DROP_LOCKS = 1
 #: dint_state_verify flags
 VERIFY_RECLAIM = 1
+#: dint_state_compact flags
+COMPACT_DRY_RUN = 1
 #: bytes of a table's control block in a TablesView (include/dint_driver.h DINT_VIEW_CTL_BYTES)
 VIEW_CTL_BYTES = 1600
 
@@ -122,6 +124,18 @@ class TableVerify(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class TableCompact(C.Structure):
+    """dint_table_compact (include/dint_abi.h)"""
+    _fields_ = [("verify", TableVerify)] + [(k, C.c_uint64) for k in (
+        "rows", "entries_before", "entries_after", "overflow_before", "overflow_after", "pool_top_before", "pool_top_after",
+        "holes_before", "holes_after", "buckets_rewritten", "unaccounted_dropped", "staging_bytes")] + [("reserved", C.c_uint64 * 20)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ("reserved", "verify")}
+        d["verify"] = self.verify.as_dict()
+        return d
 
 
 class TableView(C.Structure):
@@ -221,6 +235,7 @@ def load() -> C.CDLL:
         "dint_state_rehash": (C.c_int, [vp, C.POINTER(vp), u32, u32, C.POINTER(RehashStats), vp]),
         "dint_state_stats": (C.c_int, [vp, C.POINTER(TableStats), u32, vp]),
         "dint_state_verify": (C.c_int, [vp, C.POINTER(TableVerify), u32, u32, vp]),
+        "dint_state_compact": (C.c_int, [vp, C.POINTER(TableCompact), u32, u32, vp]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
         # ... and the state sync's rules (csrc/state_sync.h) over dumped rows
@@ -234,6 +249,9 @@ def load() -> C.CDLL:
         # ... and the table verify's rule (csrc/state_verify.h) over tables the caller describes, in host / in device memory
         "dint_state_verify_view_host": (C.c_int, [C.POINTER(TablesView), C.POINTER(TableVerify), u32, u32]),
         "dint_state_verify_view": (C.c_int, [i32, C.POINTER(TablesView), C.POINTER(TableVerify), u32, u32, vp]),
+        # ... and the compaction's rule (csrc/state_compact.h) over the same views
+        "dint_state_compact_view_host": (C.c_int, [C.POINTER(TablesView), C.POINTER(TableCompact), u32, u32]),
+        "dint_state_compact_view": (C.c_int, [i32, C.POINTER(TablesView), C.POINTER(TableCompact), u32, u32, vp]),
         # ... and the rehash's layout rule (csrc/state_rehash.h) over keys in source order
         "dint_state_rehash_place_host": (i64, [vp, u64, u64, u32, u32, vp, vp, vp]),
     }

@@ -185,6 +185,30 @@ void dint_launch_state_verify(const dint_kv &kv, dint_verify_scratch s, uint32_t
 int dint_verify_collect(const dint_kv &kv, dint_verify_scratch s, uint32_t flags, hipStream_t st, struct dint_table_verify *out,
                         uint64_t *reclaimed);
 
+// a dint_tables_view (include/dint_driver.h) checked, then as the launchers and the host forms take tables: no device memory of its
+// own.  0, or DINT_EINVAL with dint_last_error set (out: only compared with null)
+struct dint_tables_view;
+int dint_view_kv(const dint_tables_view *v, const void *out, uint32_t cap_tables, dint_kv *kv);
+
+// ---- table compaction (k_compact.hip; state_compact.h): chains packed, the pool's used part made one range, in place -----------
+struct dint_compact_scratch {
+  uint32_t *rows = nullptr;              // [sum of n_local] the valid rows of every bucket, table after table
+  void *blk_a = nullptr, *blk_b = nullptr;  // [blocks] per 256 buckets {overflow entries afterwards, buckets to rewrite} / {inline entries linked, buckets with a row}
+  uint64_t *blk_off = nullptr;           // [blocks] the exclusive scan of the overflow entries, per table
+  uint64_t *blk_junk = nullptr;          // [blocks] the second scan's offsets (only its totals are used)
+  unsigned long long *sums = nullptr;    // [DINT_KV_MAX_TABLES][4] the four totals of every table
+  uint8_t *stage[DINT_KV_MAX_TABLES] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // the staging buffers: stage_cap[t] entries, grown to what a call needs and kept
+  uint32_t stage_cap[DINT_KV_MAX_TABLES] = {0, 0, 0, 0, 0};
+};
+int dint_compact_alloc(const dint_kv &kv, dint_compact_scratch &s);
+void dint_compact_free(dint_compact_scratch &s);
+// census (vs: dint_verify_alloc'ed), count, scans and -- unless flags has DINT_COMPACT_DRY_RUN -- move and commit, then the one
+// synchronisation and out[t] for every table; a staging buffer that is too small is grown (the kernels have done nothing then) and
+// the call repeated.  ev (may be null): five events around the four stages.  0, DINT_ESTATE (gate), DINT_ENOMEM, DINT_EHIP
+struct dint_table_compact;
+int dint_compact_run(const dint_kv &kv, dint_verify_scratch vs, dint_compact_scratch &s, uint32_t flags, hipStream_t st,
+                     struct dint_table_compact *out, hipEvent_t *ev);
+
 // ---- state image (k_image.hip; state_image.h): the tables written out for another shard layout and read back --------
 struct dint_image_scratch {
   unsigned long long *words;  // [DINT_IMAGE_WORDS] device words: [2 t] table t's overflow entries, [2 t + 1] its valid slots,

@@ -139,6 +139,9 @@ struct dint_engine {
   // table verify (dint_state_verify): the owner words, partial reports and reclaim arrays, allocated on the first call and kept
   dint_verify_scratch tverify{};
   hipEvent_t ev_verify[4] = {};  // with dint_timing_enable: before the chain stage, behind it, behind the lists, behind pool stage and sum
+  // table compaction (dint_state_compact): row counts, scans and the staging buffers, allocated on the first call and kept
+  dint_compact_scratch tcompact{};
+  hipEvent_t ev_compact[5] = {};  // with dint_timing_enable: around the census, the count and its scans, the move, the commit
   // state image (dint_state_export / dint_state_import): scratch, grown on demand; `blank` = created or reset and since then
   // nothing but imports (what dint_state_import asks of its destination); the (source index, source count) pieces imported
   dint_image_scratch image{};
@@ -925,6 +928,7 @@ void dint_engine_destroy(dint_engine_t *e) {
   hipFree(e->tstats.part); hipFree(e->tstats.out);
   e->tstats = dint_stats_scratch{};
   dint_verify_free(e->tverify);
+  dint_compact_free(e->tcompact);
   image_free(e);
   rehash_free(e);
   for (hipEvent_t ev : e->ev_replay)
@@ -932,6 +936,8 @@ void dint_engine_destroy(dint_engine_t *e) {
   for (hipEvent_t ev : e->ev_rehash)
     if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : e->ev_verify)
+    if (ev) hipEventDestroy(ev);
+  for (hipEvent_t ev : e->ev_compact)
     if (ev) hipEventDestroy(ev);
   hipFree(e->d_lock_tbl);
   hipFree(e->log.ring);
@@ -1620,6 +1626,35 @@ int dint_state_verify(dint_engine_t *e, dint_table_verify *out, uint32_t cap_tab
       float ms = 0;
       HIP_TRY(hipEventElapsedTime(&ms, e->ev_verify[k], e->ev_verify[k + 1]));
       out[0].reserved[11 + k] = (uint64_t)(ms * 1e6);
+    }
+  return rc ? rc : (int)e->kv.n_tables;
+}
+
+int dint_state_compact(dint_engine_t *e, dint_table_compact *out, uint32_t cap_tables, uint32_t flags, void *stream) {
+  if (!e || !out) return fail(DINT_EINVAL, "null argument");
+  if (flags & ~DINT_COMPACT_DRY_RUN) return fail(DINT_EINVAL, "unknown flags %#x", flags);
+  if (int rc = state_check(e, true)) return rc;
+  if (cap_tables < e->kv.n_tables) return fail(DINT_EINVAL, "%u tables, room for %u", e->kv.n_tables, cap_tables);
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = dint_verify_alloc(e->kv, e->tverify, 0)) return rc;
+  if (int rc = dint_compact_alloc(e->kv, e->tcompact)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  const bool timed = e->timer.on;  // stage times: a diagnostic, in out[0].reserved[0..3]
+  if (timed)
+    for (hipEvent_t &ev : e->ev_compact)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  // (a compaction adds nothing to the tables: a blank engine stays blank, any other stays what it was)
+  const int rc = dint_compact_run(e->kv, e->tverify, e->tcompact, flags, st, out, timed ? e->ev_compact : nullptr);
+  if (rc == DINT_EHIP) return rc;
+  if (int rc2 = mark_stream(e, st)) return rc2;
+  if (timed && (rc == 0 || rc == DINT_ESTATE))
+    for (int k = 0; k < 4; k++) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, e->ev_compact[k], e->ev_compact[k + 1]));
+      out[0].reserved[k] = (uint64_t)(ms * 1e6);
     }
   return rc ? rc : (int)e->kv.n_tables;
 }

@@ -405,7 +405,7 @@ static int sv_view_bad(const char *what, uint32_t t) {
   return DINT_EINVAL;
 }
 // the view's own consistency; then kv = the tables as the launchers and the host form take them (no device memory of its own)
-static int sv_view_kv(const dint_tables_view *v, dint_table_verify *out, uint32_t cap_tables, dint_kv *kv) {
+int dint_view_kv(const dint_tables_view *v, const void *out, uint32_t cap_tables, dint_kv *kv) {
   if (!v || !out) {
     dint_set_last_error("null argument");
     return DINT_EINVAL;
@@ -453,7 +453,7 @@ static int sv_view_kv(const dint_tables_view *v, dint_table_verify *out, uint32_
 extern "C" int dint_state_verify_view(int32_t device, const dint_tables_view *view, dint_table_verify *out, uint32_t cap_tables,
                                       uint32_t flags, void *stream) {
   dint_kv kv;
-  if (int rc = sv_view_kv(view, out, cap_tables, &kv)) return rc;
+  if (int rc = dint_view_kv(view, out, cap_tables, &kv)) return rc;
   if (hipSetDevice(device) != hipSuccess) {
     dint_set_last_error("table view: no such device");
     return DINT_EHIP;
@@ -515,7 +515,7 @@ struct sv_host_list {
 
 extern "C" int dint_state_verify_view_host(const dint_tables_view *view, dint_table_verify *out, uint32_t cap_tables, uint32_t flags) {
   dint_kv kv;
-  if (int rc = sv_view_kv(view, out, cap_tables, &kv)) return rc;
+  if (int rc = dint_view_kv(view, out, cap_tables, &kv)) return rc;
   uint64_t h[DINT_KV_MAX_TABLES][SV_WORDS];
   memset(h, 0, sizeof h);
   std::vector<uint32_t> leaked[DINT_KV_MAX_TABLES];

@@ -313,6 +313,22 @@ class Engine:
         reports also then."""
         return self.state_verify(stream, reclaim=True)
 
+    # ---- table compaction (dint_state_compact) ---------------------------------------------------------------
+    def state_compact(self, stream: int = 0, dry_run: bool = False) -> list:
+        """dint_state_compact: every bucket's valid rows packed, in chain order, into its inline entry and as few overflow
+        entries as they need, the overflow entries laid end to end from pool entry 0, pool_top lowered to them and the free
+        and pend lists emptied -- in place, lock words untouched (include/dint_abi.h; csrc/state_compact.h is the rule).  Per
+        table a dict: the census before the move under "verify", then rows, entries_before / _after, overflow_before /
+        _after, pool_top_before / _after, holes_before / _after, buckets_rewritten, unaccounted_dropped, staging_bytes.
+        dry_run=True fills the same report and writes nothing.  Raises DintError (DINT_ESTATE) with not a byte written when
+        the census finds a violation; `last_compact` holds the reports also then."""
+        s = (_lib.TableCompact * 5)()
+        rc = self._L.dint_state_compact(self._h, s, 5, _lib.COMPACT_DRY_RUN if dry_run else 0, stream)
+        self.last_compact = [s[t].as_dict() for t in range(_N_TABLES.get(self.workload, 0))]
+        self.last_compact_stage_ns = dict(zip(("census", "count", "move", "commit"), list(s[0].reserved)[:4]))  # with timing_enable on
+        n = _lib.check(rc)
+        return self.last_compact[:n]
+
     def stats(self) -> dict:
         s = _lib.Stats()
         _lib.check(self._L.dint_get_stats(self._h, C.byref(s)))

@@ -331,6 +331,64 @@ def rehash_advice(engines, rows_per_bucket=8 / 3, max_rows_per_bucket=4.0, max_p
             "load": load, "pool_fill": pool_fill, "locks_held": sum(t["locks_held"] for t in tables), "tables": tables}
 
 
+def compact_tables(engines, dry_run: bool = False) -> dict:
+    """Engine.state_compact of every engine of a set -- a shard set, or any engines of one workload -- and the reports added up
+    per table, as verify_tables does for the census: every count adds ("verify": as verify_tables adds it).  Returns {"tables":
+    the sums per table, "engines": the reports per engine}.  A refused compaction raises DintError like the engine call; the
+    engines before it are compacted then (dry_run=True first, to ask every engine before any is touched)."""
+    per = [e.state_compact(dry_run=dry_run) for e in engines]
+    tables = None
+    for rep in per:
+        if tables is None:
+            tables = [dict(x, verify=dict(x["verify"])) for x in rep]
+            continue
+        for x, y in zip(tables, rep):
+            for k in x:
+                if k != "verify":
+                    x[k] += y[k]
+            for k in x["verify"]:
+                x["verify"][k] = max(x["verify"][k], y["verify"][k]) if k == "longest_list" else x["verify"][k] + y["verify"][k]
+    return {"tables": tables or [], "engines": per}
+
+
+def compact_advice(engines, rows_per_bucket=8 / 3, max_rows_per_bucket=4.0, max_pool_fill=0.5, max_hole_share=0.25,
+                   max_pool_top_fill=0.75) -> dict:
+    """Compact this set of engines in place, rehash it, or leave it?  Policy only: one Engine.state_stats and one dry run of
+    Engine.state_compact per engine, nothing written.  rehash_advice is not changed by this and still answers its own question.
+
+    "rehash"   the bucket count itself is too small: a table's load (rows over the set / GLOBAL bucket count) exceeds
+               max_rows_per_bucket, or some table of some engine would still have more than max_pool_fill of its pool linked
+               AFTER a compaction (overflow_after / pool_cap) -- its chains need more buckets, not a tidier layout
+    "compact"  otherwise, when the layout has decayed: hole_share -- the slots a compaction gives back, (holes_before -
+               holes_after) / (4 * entries_before), the largest over tables and engines -- exceeds max_hole_share, or
+               pool_top_fill -- min(pool_top, pool_cap) / pool_cap, the largest -- exceeds max_pool_top_fill
+    "none"     otherwise
+
+    The thresholds are ARGUMENTS, not tuned numbers: the first three are rehash_advice's; 0.25 says a quarter of the slots a
+    lookup walks past are dead weight, one header sector in four; 0.75 leaves a quarter of the pool to the bump allocator
+    before every inserting run of a pass goes request by request.  Returns {action, n_rows (rehash_advice's: what to create
+    the destinations of a rehash with), load, hole_share, pool_top_fill, pool_top_fill_after, locks_held (a rehash needs
+    drop_locks=True then; a compaction does not care), tables: table_stats, compact: compact_tables' sums}."""
+    engines = list(engines)
+    per = [e.state_stats() for e in engines]
+    dry = compact_tables(engines, dry_run=True)
+    tables = merge_table_stats(per)
+    load = [t["rows"] / engines[0].hash_size(k) for k, t in enumerate(tables)]
+    each = [(c, s["pool_cap"]) for rep, srep in zip(dry["engines"], per) for c, s in zip(rep, srep)]
+    hole_share = max(((c["holes_before"] - c["holes_after"]) / (4 * c["entries_before"]) for c, _ in each if c["entries_before"]), default=0.0)
+    top_fill = max((min(c["pool_top_before"], cap) / cap for c, cap in each if cap), default=0.0)
+    fill_after = max((c["overflow_after"] / cap for c, cap in each if cap), default=0.0)
+    if any(x > max_rows_per_bucket for x in load) or fill_after > max_pool_fill:
+        action = "rehash"
+    elif hole_share > max_hole_share or top_fill > max_pool_top_fill:
+        action = "compact"
+    else:
+        action = "none"
+    return {"action": action, "n_rows": advise_n_rows(engines[0].workload, [t["rows"] for t in tables], rows_per_bucket),
+            "load": load, "hole_share": hole_share, "pool_top_fill": top_fill, "pool_top_fill_after": fill_after,
+            "locks_held": sum(t["locks_held"] for t in tables), "tables": tables, "compact": dry["tables"]}
+
+
 def save_state(engine, path) -> dict:
     """The engine's own image -- (i, G) -> (i, G): tables, chains and lock words -- written to a file.  The log ring is NOT
     part of it (nor are the pool's free lists): drain the log first if its records matter."""

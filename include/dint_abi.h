@@ -495,6 +495,44 @@ typedef struct dint_table_verify {
  * lock_fasst / lock_2pl / log engine, a batch announced by dint_submit_device_ahead pending (DINT_ESTATE).  No content of the
  * tables makes the kernels read or write outside them or loop without bound.  The caller keeps the engine quiet meanwhile. */
 int dint_state_verify(dint_engine_t *e, dint_table_verify *out, uint32_t cap_tables, uint32_t flags, void *stream);
+/* ---- table compaction (v5, additive): chains packed and the overflow pool made one range, IN PLACE -------------------------
+ * What puts right what dint_state_stats diagnoses, without a second engine: at the same bucket count and shard no row changes
+ * its bucket, so each bucket's valid rows, in chain order, are packed into its inline entry and as few overflow entries as they
+ * need, the overflow entries of all buckets laid end to end from pool entry 0 (dint_amd/csrc/state_compact.h is the rule:
+ * dint_state_rehash's layout applied to the engine itself).  pool_top falls to the overflow entries linked; the free and pend
+ * lists are emptied (their tags bumped); holes, entries without a valid slot, leaked entries and everything on the lists are
+ * dropped.  Chain order is kept, so every key's visible row stays its visible row, and the tatp lock bytes and owner keys and
+ * smallbank's counters in the inline entries keep their bytes: an engine that holds locks can be compacted.  The census of
+ * dint_state_verify runs first, in the same call. */
+#define DINT_COMPACT_DRY_RUN 1u /* dint_state_compact flags: fill the report with what a compaction would do; write nothing */
+typedef struct dint_table_compact {
+  dint_table_verify verify;     /* the census BEFORE the move (reclaimed = stray_rows_cleared = 0) */
+  uint64_t rows;                /* valid rows: every one is kept.  This field and the eleven below are 0 in a refused call */
+  uint64_t entries_before, entries_after;   /* entries linked into chains, linked inline entries included */
+  uint64_t overflow_before, overflow_after; /* the pool entries among them */
+  uint64_t pool_top_before, pool_top_after; /* before: raw, also above pool_cap; after = overflow_after */
+  uint64_t holes_before, holes_after;       /* 4 * entries - rows */
+  uint64_t buckets_rewritten;   /* buckets whose chain was not yet inline entry first, every entry full but the last */
+  uint64_t unaccounted_dropped; /* leaked pool entries that fell below the new pool_top's tail: verify.unaccounted */
+  uint64_t staging_bytes;       /* overflow_after * stride: what the table's staging buffer must hold */
+  uint64_t reserved[20];        /* out[0].reserved[0..3], with dint_timing_enable: nanoseconds of the census, the count and its scans, the
+                                   move, the commit, all tables, between events */
+} dint_table_compact;
+/* (v5, additive) out[t] for every table t of the workload (1 / 5 / 2); returns that number (cap_tables smaller: DINT_EINVAL).
+ * Synchronous like dint_state_verify: orders itself behind the engine's pending work on `stream` (NULL = the engine's own).  The
+ * moving kernels read the census on the device, so the call makes one host synchronisation -- two when a table's staging buffer
+ * (engine scratch of staging_bytes, allocated by the first call that needs it and kept) has to grow: the kernels do nothing
+ * then, and the call runs again with a buffer that fits.  A blank engine stays blank; a second compaction changes nothing but
+ * the lists' tags.  Refused, with not a byte written:
+ *   DINT_ESTATE  bad_chains, cross_linked, linked_beyond_top, list_bad_links, stray_valid_entries, misplaced_rows or
+ *                odd_valid_bytes non-zero in any table (`out` holds the census; unaccounted entries are no violation); a
+ *                lock_fasst / lock_2pl / log engine; a batch announced by dint_submit_device_ahead pending
+ *   DINT_ENOMEM  a staging buffer cannot be allocated
+ *   DINT_EINVAL  an unknown flag, cap_tables too small
+ * dint_snapshot captures the tables, pool_next and the control words (pool_top, every head word), so a snapshot taken before a
+ * compaction restores the engine as it was before it.  No content of the tables makes the kernels read or write outside them
+ * and the staging buffer or loop without bound.  The caller keeps the engine quiet meanwhile. */
+int dint_state_compact(dint_engine_t *e, dint_table_compact *out, uint32_t cap_tables, uint32_t flags, void *stream);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

@@ -259,6 +259,18 @@ int dint_state_verify_view_host(const dint_tables_view *view, struct dint_table_
 int dint_state_verify_view(int32_t device, const dint_tables_view *view, struct dint_table_verify *out, uint32_t cap_tables,
                            uint32_t flags, void *stream);
 
+/* ---- table compaction: the rule over caller-provided memory (dint_amd/csrc/state_compact.h) ---------------------------------
+ * dint_state_compact (include/dint_abi.h) over tables the CALLER describes, with the view and its check of the verify forms
+ * above (a view that fails it: DINT_EINVAL).  out, cap_tables, flags (DINT_COMPACT_DRY_RUN) and the return value are
+ * dint_state_compact's; a view whose census fails the gate is refused with DINT_ESTATE and not a byte of it changes.
+ * dint_state_compact_view_host: host pointers, no device call.  dint_state_compact_view: device pointers on `device`; the same
+ * launchers as the engine call, scratch and staging buffer allocated and freed by the call, `stream` (NULL: the null stream)
+ * synchronised once per round (two rounds whenever an overflow entry remains: the first sizes the staging buffer). */
+struct dint_table_compact; /* include/dint_abi.h */
+int dint_state_compact_view_host(const dint_tables_view *view, struct dint_table_compact *out, uint32_t cap_tables, uint32_t flags);
+int dint_state_compact_view(int32_t device, const dint_tables_view *view, struct dint_table_compact *out, uint32_t cap_tables,
+                            uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,10 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -163,6 +165,10 @@ struct dint_engine {
     int set = 0;  // lock tables: the scratch set (0 = `scratch`, 1 = lp.set[1]) the announced batch's count stage filled
     uint32_t seg_cap = 0, n_seg = 0;  // a segmented batch (dint_submit_segments_multi_ahead): its geometry
     const void *cnt = nullptr;
+    // a launch set's announcement: one word shared by the engines of the set.  The set is answered by all of them or by none,
+    // so the first of them whose announcement is cancelled says so here, and the others drop theirs when they are next
+    // looked at (ahead_settle)
+    std::shared_ptr<std::atomic<bool>> broken;
   } ahead;
 
   // snapshot
@@ -368,6 +374,8 @@ int run_lock_pass_piped(dint_engine *e, const void *d_req, uint32_t n, void *d_r
 int ahead_cancel(dint_engine *e) {
   if (!e->ahead.valid) return 0;
   e->ahead.valid = false;
+  if (e->ahead.broken) e->ahead.broken->store(true);
+  e->ahead.broken.reset();
   HIP_TRY(hipDeviceSynchronize());
   if (!e->kv.n_tables) {  // a lock engine: the counters, the big-bin list and the region names of the set the count stage filled
     dint_scratch &ls = e->ahead.set == 0 ? e->scratch : e->lp.set[e->ahead.set];
@@ -394,10 +402,19 @@ int ahead_cancel(dint_engine *e) {
   return 0;
 }
 
+// An engine of a launch set whose announcement another engine of the set has cancelled: the set will not be answered as
+// announced, so this engine's share of it is cancelled too, silently (the caller that broke the set was told).
+int ahead_settle(dint_engine *e) {
+  if (!e->ahead.valid || !e->ahead.broken || !e->ahead.broken->load()) return 0;
+  HIP_TRY(hipSetDevice(e->device));  // (some callers look before they have chosen the device)
+  return ahead_cancel(e);
+}
+
 int run_pass(dint_engine *e, const void *d_req, uint32_t n, void *d_rep, hipStream_t st, int load_mode = 0,
              const dint_view &view = dint_flat_view(), bool inputs_ready = false, const dint_kv_ahead *next = nullptr) {
   bool part_done = false;
   e->blank = false;
+  if (int rc = ahead_settle(e)) return rc;
   if (e->ahead.valid) {  // the pass that was announced, and nothing else
     if (e->ahead.req != d_req || e->ahead.rep != d_rep || e->ahead.n != n || view.seg_cap != e->ahead.seg_cap || load_mode) {
       if (int rc = ahead_cancel(e)) return rc;
@@ -405,6 +422,7 @@ int run_pass(dint_engine *e, const void *d_req, uint32_t n, void *d_rep, hipStre
                                "submission; its log records are appended already", e->ahead.n, e->ahead.req);
     }
     e->ahead.valid = false;
+    e->ahead.broken.reset();
     part_done = true;
   }
   if (int rc = order_stream(e, st)) return rc;
@@ -471,6 +489,7 @@ int run_pass(dint_engine *e, const void *d_req, uint32_t n, void *d_rep, hipStre
         e->ahead.valid = true;
         e->ahead.req = next->d_req; e->ahead.rep = next->d_rep; e->ahead.n = next->n;
         e->ahead.seg_cap = 0; e->ahead.n_seg = 0; e->ahead.cnt = nullptr;
+        e->ahead.broken.reset();
       }
       break;
     default:
@@ -588,7 +607,8 @@ int state_check(const dint_engine *e, bool sharded_ok) {
   return 0;
 }
 // ... under the engine's mutex: the state calls read the tables where they lie, so none runs between an announcement and its pass
-int state_quiet(const dint_engine *e) {
+int state_quiet(dint_engine *e) {
+  if (int rc = ahead_settle(e)) return rc;
   return e->ahead.valid ? fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending") : 0;
 }
 // ... after a launcher
@@ -954,6 +974,7 @@ int submit_device_locked(dint_engine *e, const void *d_reqs, uint32_t n, void *d
   hipStream_t st = stream ? (hipStream_t)stream : e->stream;
   const uint8_t *rq = (const uint8_t *)d_reqs;
   uint8_t *rp = (uint8_t *)d_replies;
+  if (int rc = ahead_settle(e)) return rc;
   if (n == 0 && e->ahead.valid) return run_pass(e, d_reqs, 0, d_replies, st);  // (reports the broken announcement)
   for (uint32_t off = 0; off < n; off += e->pass_max) {
     uint32_t m = std::min<uint32_t>(e->pass_max, n - off);
@@ -1025,7 +1046,9 @@ int dint_submit_segments_multi_ahead(const dint_segments_item *items, uint32_t n
     const uint32_t wl = e->cfg.workload;
     one_set = (wl == DINT_WL_STORE || wl == DINT_WL_TATP || wl == DINT_WL_SMALLBANK) && wl == items[0].engine->cfg.workload &&
               e->device == items[0].engine->device && items[k].n_seg > 0 && items[k].seg_cap >= 2 &&
-              (uint64_t)items[k].n_seg * items[k].seg_cap <= e->pass_max;
+              (uint64_t)items[k].n_seg * items[k].seg_cap <= e->pass_max &&
+              // (the launch takes `hot` and the workers from the first engine: all must resolve hot keys the same way)
+              !((e->cfg.flags ^ items[0].engine->cfg.flags) & (DINT_FLAG_KV_ROUNDS | DINT_FLAG_KV_NO_HOT | DINT_FLAG_LOCK_SAME_KEY));
   }
   if (!one_set) {
     for (uint32_t k = 0; k < n_items; k++)
@@ -1057,6 +1080,7 @@ int dint_submit_segments_multi_ahead(const dint_segments_item *items, uint32_t n
   // what ran ahead: all of the engines' partitions (the previous call of this kind announced exactly this step), or none
   uint32_t n_done = 0;
   for (uint32_t k = 0; k < n_items; k++) {
+    if (int rc = ahead_settle(items[k].engine)) return rc;
     const dint_engine::Ahead &a = items[k].engine->ahead;
     if (a.valid && a.req == items[k].d_base && a.n == items[k].n_seg * items[k].seg_cap && a.seg_cap == items[k].seg_cap &&
         a.n_seg == items[k].n_seg && a.cnt == items[k].d_cnt)
@@ -1070,7 +1094,12 @@ int dint_submit_segments_multi_ahead(const dint_segments_item *items, uint32_t n
     return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead / dint_submit_segments_multi_ahead must be the engine's next submission");
   }
   const bool part_done = n_done == n_items;
-  for (uint32_t k = 0; k < n_items; k++) items[k].engine->ahead.valid = false;
+  for (uint32_t k = 0; k < n_items; k++) {
+    items[k].engine->ahead.valid = false;
+    items[k].engine->ahead.broken.reset();
+  }
+  std::shared_ptr<std::atomic<bool>> set_word;
+  if (next) set_word = std::make_shared<std::atomic<bool>>(false);
   for (uint32_t k = 0; k < n_items; k++) {
     const dint_segments_item &it = items[k];
     dint_engine *e = it.engine;
@@ -1098,6 +1127,7 @@ int dint_submit_segments_multi_ahead(const dint_segments_item *items, uint32_t n
       e->ahead.valid = true;
       e->ahead.req = next[k].d_base; e->ahead.rep = next[k].d_base; e->ahead.n = pass[k].n;
       e->ahead.seg_cap = items[k].seg_cap; e->ahead.n_seg = items[k].n_seg; e->ahead.cnt = next[k].d_cnt;
+      e->ahead.broken = set_word;
     }
   }
   return 0;
@@ -1480,6 +1510,7 @@ int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, u
   if (wl != DINT_WL_TATP && wl != DINT_WL_SMALLBANK) return fail(DINT_ESTATE, "workload has no table a log replays into");
   if (e->shard.count > 1) return fail(DINT_EINVAL, "a sharded engine: the log would have to be routed first");
   std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = ahead_settle(e)) return rc;
   if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
   HIP_TRY(hipSetDevice(e->device));
   if (chunk == 0 || chunk > e->pass_max) chunk = e->pass_max;
@@ -2103,6 +2134,7 @@ int dint_snapshot(dint_engine_t *e) {
   std::lock_guard<std::mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());
+  if (int rc = ahead_settle(e)) return rc;
   if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending (its log records are appended)");
   if (e->kv.n_tables && e->log.tail) {  // both tail words say where the ring stands: whatever the parity of the passes after a restore
     uint32_t t[2];

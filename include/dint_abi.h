@@ -199,7 +199,7 @@ void dint_free_pinned(void *p);
  * CALLER enqueues on other streams (producing d_reqs, consuming d_replies) is the caller's to order --
  * dint_stream_wait / dint_stream_signal do that for the engine's own stream. */
 int dint_submit_device(dint_engine_t *e, const void *d_reqs, uint32_t n, void *d_replies, void *stream);
-/* The same with a LOOK-AHEAD (round 6; store / tatp / lock_fasst / lock_2pl -- smallbank and log_server ignore the announcement): (d_next_reqs, next_n,
+/* The same with a LOOK-AHEAD (round 6; store / tatp / smallbank / lock_fasst / lock_2pl -- log_server ignores the announcement): (d_next_reqs, next_n,
  * d_next_replies) is the batch of the engine's NEXT dint_submit_device[_ahead] call.  The caller promises that (1) that call
  * will be made, with exactly these pointers and this count, before anything else is submitted to the engine, (2) the
  * batch's request bytes are complete in device memory in the order of `stream` -- produced by work enqueued on `stream`
@@ -587,8 +587,9 @@ int dint_submit_segments(dint_engine_t *e, void *d_base, uint32_t n_seg, uint32_
  * closed-loop epoch or an exchange step hands every server its batch at the same moment; with one stream per engine that
  * is a fork and a join across streams per step, with this call it is three launches on the caller's stream (NULL: the
  * first engine's).  Every engine appears at most once in `items` (DINT_EINVAL otherwise).  Each engine's history is what dint_submit_segments would have produced.  Batches that do not fit one
- * kernel pass (n_seg * seg_cap > max_pass), lock / log engines and more than 4 items fall back to one
- * dint_submit_segments per item on that stream. */
+ * kernel pass (n_seg * seg_cap > max_pass), lock / log engines, more than 4 items, and engines that do not agree in
+ * DINT_FLAG_KV_ROUNDS, DINT_FLAG_KV_NO_HOT and DINT_FLAG_LOCK_SAME_KEY (one launch resolves every engine's hot keys the same
+ * way) fall back to one dint_submit_segments per item on that stream; an announcement is then dropped. */
 typedef struct dint_segments_item {
   dint_engine_t *engine;
   void *d_base;
@@ -602,7 +603,11 @@ int dint_submit_segments_multi(const dint_segments_item *items, uint32_t n_items
  * this kind -- the same engines in the same order, the same geometry (n_seg, seg_cap, strides), other buffers, complete in
  * device memory in the order of `stream` (the exchange has delivered them).  The engines' partitions of that step ride in this
  * step's launch set.  next == NULL, or an announcement that does not fit (other engines, another geometry, a workload without
- * the one-launch pass): plain dint_submit_segments_multi.  The announced step MUST be the engines' next submission. */
+ * the one-launch pass): plain dint_submit_segments_multi.  The announced step MUST be the engines' next submission: it is
+ * answered by all of the engines or by none.  Anything else submitted to one of them in between fails with DINT_ESTATE as
+ * after dint_submit_device_ahead and cancels the announcement of EVERY engine of the set (the others drop theirs when they
+ * are next called); the announced buffers then hold what the first stage wrote (log requests answered in place) and the
+ * step is handed over again with its requests. */
 int dint_submit_segments_multi_ahead(const dint_segments_item *items, uint32_t n_items, const dint_segments_item *next, void *stream);
 /* d_home[i] = home shard (0..shard_count-1) of d_reqs[i], computed on the GPU with the
  * same hash/modulus the engine uses; 0xFF for requests that have no home (bad table). */

@@ -203,7 +203,8 @@ def test_a_broken_announcement_is_an_error_and_the_engine_stays_usable():
     assert d2.cpu().numpy().tobytes() == o2.replay(req[:1000]).tobytes()
 
 
-def test_smallbank_and_lock_tables_ignore_the_announcement():
+def test_smallbank_and_lock_tables_answer_announced_batches_as_the_oracle_does():
+    """(smallbank passes take an announcement since r06 -- dint_kv_ahead_ok -- and so do the lock tables: k_lock_pass)"""
     req = tracegen.sb_random(80_000, seed=4, n_acct_touch=30)
     o = orc.SmallbankOracle(10_000, populate_n=60)
     eng = _engine(W.SMALLBANK, n_rows=10_000)

@@ -13,6 +13,7 @@ import torch
 import shard_double as sd
 import tracegen
 from dint_amd import wire
+from kv_multi import _segmented, _unsegment  # (the segment layout: shared with tests/test_gpu_kv_multi.py)
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -133,25 +134,6 @@ def test_route_multi_equals_per_engine_calls(sizes, world):
         want.append(w.tobytes())
     assert a[2] == b[2] and a[2] == want
     assert a[3] == b[3] and a[3][0] == 0 and (a[3][1] > 0) == (sizes[1] > 0)  # only the second server's slots are too small
-
-
-def _segmented(req: np.ndarray, cuts, cap, hdr=64):
-    """lay `req` out as len(cuts)-1 segments of capacity `cap` with a header in front of each"""
-    msg = req.dtype.itemsize
-    stride = hdr + (cap * msg + 63) // 64 * 64
-    nseg = len(cuts) - 1
-    buf = np.full(nseg * stride, 0xCD, np.uint8)  # padding slots hold garbage
-    for k in range(nseg):
-        part = req[cuts[k]:cuts[k + 1]]
-        buf[k * stride:k * stride + 4] = np.array([len(part)], "<u4").view(np.uint8)
-        buf[k * stride + hdr:k * stride + hdr + len(part) * msg] = np.frombuffer(part.tobytes(), np.uint8)
-    return buf, stride, nseg
-
-
-def _unsegment(buf, cuts, stride, dtype, hdr=64):
-    msg = dtype.itemsize
-    return np.concatenate([np.frombuffer(buf[k * stride + hdr:k * stride + hdr + (cuts[k + 1] - cuts[k]) * msg].tobytes(), dtype)
-                           for k in range(len(cuts) - 1)])
 
 
 @pytest.mark.parametrize("wl", ["fasst", "tpl", "tatp", "smallbank"])

@@ -26,10 +26,12 @@ SYMBOLS = [
     "dint_stream_wait", "dint_stream_signal", "dint_route_pack", "dint_route_unpack", "dint_submit_segments",
     "dint_log_drain", "dint_refuse", "dint_route_pack_multi", "dint_route_unpack_multi", "dint_bench_access", "dint_selftest",
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
-    "dint_log_drain_device", "dint_log_apply_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
+    "dint_log_drain_device", "dint_log_apply_device", "dint_log_apply_folded_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
     "dint_state_export", "dint_state_import", "dint_state_rehash", "dint_state_stats",
     "dint_state_verify", "dint_state_compact",
 ]
+#: dint_log_apply_folded_device flags
+FOLD_DRY_RUN = 1
 #: dint_state_rehash flags
 REHASH_DROP_LOCKS = 1
 #: dint_state_verify flags
@@ -69,6 +71,18 @@ class ApplyStats(C.Structure):
     """dint_apply_stats (include/dint_abi.h)"""
     _fields_ = [("applied", C.c_uint64), ("commits", C.c_uint64), ("inserts", C.c_uint64), ("deletes", C.c_uint64),
                 ("chunks", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class FoldStats(C.Structure):
+    """dint_fold_stats (include/dint_abi.h)"""
+    _fields_ = [(k, C.c_uint64) for k in (
+        "applied", "commits", "inserts", "deletes", "chunks", "rows", "folded_records", "deferred_records", "deferred_buckets",
+        "repair_records", "updated", "inserted", "deleted", "refused")] + [("ns", C.c_uint64 * 4), ("reserved", C.c_uint64 * 5)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ("ns", "reserved")}
+        d["stage_ns"] = dict(zip(("sort", "fold", "repair", "deferred"), list(self.ns)))
+        return d
 
 
 class TableDigest(C.Structure):
@@ -227,6 +241,7 @@ def load() -> C.CDLL:
         "dint_refuse": (C.c_int, [u32, vp, u32, vp]),
         "dint_log_drain_device": (i64, [vp, vp, u64, C.POINTER(u64), vp]),
         "dint_log_apply_device": (C.c_int, [vp, vp, u64, u32, C.POINTER(ApplyStats)]),
+        "dint_log_apply_folded_device": (C.c_int, [vp, vp, u64, u32, u32, C.POINTER(FoldStats)]),
         "dint_state_digest": (C.c_int, [vp, C.POINTER(TableDigest), u32, vp]),
         "dint_state_diff": (i64, [vp, vp, vp, u64, C.POINTER(DiffStats), vp]),
         "dint_state_repair": (C.c_int, [vp, vp, u64, C.POINTER(RepairStats), vp]),
@@ -238,6 +253,7 @@ def load() -> C.CDLL:
         "dint_state_compact": (C.c_int, [vp, C.POINTER(TableCompact), u32, u32, vp]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
+        "dint_log_fold_host": (i64, [u32, u32, vp, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(FoldStats)]),
         # ... and the state sync's rules (csrc/state_sync.h) over dumped rows
         "dint_state_row_hash_host": (u64, [u64, u32, u32, vp, u32]),
         "dint_state_digest_host": (C.c_int, [u32, vp, vp, vp, u32, u64, C.POINTER(TableDigest)]),

@@ -139,3 +139,44 @@ void dint_launch_replay_emit(const void *d_rec, uint32_t m, dint_replay_scratch 
 void dint_launch_replay_emit_sb(const void *d_rec, uint32_t m, dint_replay_scratch s, hipStream_t st);
 // after the replica answered s.msgs in place: the acks by type into s.counts
 void dint_launch_replay_count(uint32_t workload, uint32_t m, dint_replay_scratch s, hipStream_t st);
+
+// ---- log fold: k_fold.hip (dint_log_apply_folded_device; the rule is log_fold.h's) -----------------------------------------
+// scratch of one chunk of `cap` records; allocated on first use, grown when a call asks for a longer chunk
+#define DINT_FOLD_COUNTS 16u  // counts: [0..2] folded records as commits / inserts / deletes, [3..5] deferred ones, [6] deferred records,
+                              // [7] deferred buckets, [8] rows, [9] repair records, [10..13] the repair's {updated, inserted, deleted,
+                              // refused}, [14] the repair check's flag, ORed
+struct dint_fold_scratch {
+  uint32_t cap;                  // records a chunk holds at most (0 = nothing allocated)
+  uint64_t *k0, *k1;             // [cap] sort keys, in and out: lr_row, then the place words
+  uint32_t *i0, *i1;             // [cap] record indices, in and out
+  uint64_t *place_log;           // [cap] record i's place word (log_fold.h lf_place)
+  uint64_t *key_s;               // [cap] the key at sorted position p
+  uint8_t *del_s;                // [cap] is_del at sorted position p (smallbank: 0)
+  uint32_t *flag;                // [cap] scan input: row heads
+  uint32_t *delpos;              // [cap] scan input: p + 1 where the record at p is a delete
+  uint32_t *rowid;               // [cap] rows that start at or before p (p's row is rowid[p] - 1)
+  uint32_t *lastdel;             // [cap] the max-scan of delpos
+  uint32_t *row_start;           // [cap + 1] first sorted position of row r; [rows] = m
+  uint32_t *row_occ, *row_v0;    // [cap] what the probe found
+  uint32_t *row_kind, *row_ver;  // [cap] the row's net effect (log_fold.h lf_net)
+  uint8_t *row_defer;            // [cap] the row's bucket is deferred
+  uint32_t *has, *epos;          // [cap] the row emits a repair record / how many rows before it do
+  uint32_t *dflag, *dpos;        // [cap] record i is deferred / how many records before it are
+  uint8_t *repair;               // [cap] 64-byte repair records, ascending (table, bucket)
+  uint8_t *def_rec;              // [cap] the deferred records in log order
+  void *tmp;                     // temporary storage of the sorts and scans
+  size_t tmp_bytes;
+  uint32_t *words;               // device words of the chunk: {deferred records, repair records, rows}
+  unsigned long long *counts;    // [DINT_FOLD_COUNTS], summed over the chunks of a call
+};
+struct kv_dev;
+// bytes of temporary storage the sorts and scans of m records need (no GPU work); negative = error
+int64_t dint_fold_tmp_bytes(uint32_t m, hipStream_t st);
+// records [0, m) of a chunk: sort, probe, fold, the repair records into s.repair, the deferred records into s.def_rec, the
+// chunk's three words into s.words; false = a sort or scan failed
+bool dint_launch_fold(const void *d_rec, uint32_t m, uint32_t workload, const kv_dev *d_kv, dint_fold_scratch s, hipStream_t st,
+                      hipEvent_t mid);
+// in front of the repair: overflow entries freed by earlier launches become allocatable again (dint_kv_core.h kv_pool_rotate)
+void dint_launch_fold_rotate(const kv_dev *d_kv, hipStream_t st);
+// after the repair: its result words (k_state.hip: {bad, updated, inserted, deleted, refused}) added to s.counts
+void dint_launch_fold_harvest(const unsigned long long *repair_words, dint_fold_scratch s, hipStream_t st);

@@ -133,6 +133,9 @@ struct dint_engine {
   // log replay (dint_log_apply_device): scratch of one chunk, allocated on first use; the events of its stage timing
   dint_replay_scratch replay{};
   hipEvent_t ev_replay[4] = {};
+  // log fold (dint_log_apply_folded_device): scratch of one chunk, allocated on first use; the events of its stage timing
+  dint_fold_scratch fold{};
+  hipEvent_t ev_fold[5] = {};
   // state sync (dint_state_digest / dint_state_diff / dint_state_repair): result words, and -- for the diff, in engine a --
   // the per-workgroup counts; allocated on first use
   dint_state_scratch state{};
@@ -569,6 +572,43 @@ int replay_alloc(dint_engine *e, uint32_t cap) {
   return 0;
 }
 
+// log fold scratch: everything a chunk of `cap` records needs (dint_kernels.h dint_fold_scratch)
+void fold_free(dint_engine *e) {
+  dint_fold_scratch &f = e->fold;
+  void *all[] = {f.k0, f.k1, f.i0, f.i1, f.place_log, f.key_s, f.del_s, f.flag, f.delpos, f.rowid, f.lastdel, f.row_start, f.row_occ,
+                 f.row_v0, f.row_kind, f.row_ver, f.row_defer, f.has, f.epos, f.dflag, f.dpos, f.repair, f.def_rec, f.tmp, f.words,
+                 f.counts};
+  for (void *p : all) hipFree(p);
+  f = dint_fold_scratch{};
+}
+int fold_alloc(dint_engine *e, uint32_t cap) {
+  dint_fold_scratch &f = e->fold;
+  if (f.cap >= cap) return 0;
+  HIP_TRY(hipStreamSynchronize(e->stream));  // (a call that still uses the smaller set)
+  fold_free(e);
+  const int64_t tmp = dint_fold_tmp_bytes(cap, e->stream);
+  if (tmp < 0) return fail(DINT_EHIP, "log fold: temporary storage query failed");
+  const size_t n = cap;
+  int rc = 0;
+  auto get = [&](auto **p, size_t bytes, bool zero = false) {
+    if (!rc) rc = dev_alloc((void **)p, bytes, zero);
+  };
+  get(&f.k0, n * 8); get(&f.k1, n * 8); get(&f.i0, n * 4); get(&f.i1, n * 4); get(&f.place_log, n * 8); get(&f.key_s, n * 8);
+  get(&f.del_s, n); get(&f.flag, n * 4); get(&f.delpos, n * 4); get(&f.rowid, n * 4); get(&f.lastdel, n * 4);
+  get(&f.row_start, (n + 1) * 4); get(&f.row_occ, n * 4); get(&f.row_v0, n * 4); get(&f.row_kind, n * 4); get(&f.row_ver, n * 4);
+  get(&f.row_defer, n); get(&f.has, n * 4); get(&f.epos, n * 4); get(&f.dflag, n * 4); get(&f.dpos, n * 4);
+  get(&f.repair, n * 64); get(&f.def_rec, n * 64); get(&f.tmp, (size_t)tmp);
+  get(&f.words, 4 * sizeof(uint32_t), true); get(&f.counts, DINT_FOLD_COUNTS * sizeof(unsigned long long), true);
+  f.tmp_bytes = (size_t)tmp;
+  if (rc) {
+    fold_free(e);
+    return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());  // (the zero fills ran on the null stream: the engine's stream does not wait for it)
+  f.cap = cap;
+  return 0;
+}
+
 // state sync scratch: the result words always, the diff's per-workgroup arrays when asked for
 void state_free(dint_engine *e) {
   hipFree(e->state.words); hipFree(e->state.blk_cnt); hipFree(e->state.blk_off); hipFree(e->state.digest_part);
@@ -944,6 +984,7 @@ void dint_engine_destroy(dint_engine_t *e) {
   if (e->s_d2h && e->s_d2h != e->stream) hipStreamDestroy(e->s_d2h);
   lock_pipe_destroy(e);
   replay_free(e);
+  fold_free(e);
   state_free(e);
   hipFree(e->tstats.part); hipFree(e->tstats.out);
   e->tstats = dint_stats_scratch{};
@@ -952,6 +993,8 @@ void dint_engine_destroy(dint_engine_t *e) {
   image_free(e);
   rehash_free(e);
   for (hipEvent_t ev : e->ev_replay)
+    if (ev) hipEventDestroy(ev);
+  for (hipEvent_t ev : e->ev_fold)
     if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : e->ev_rehash)
     if (ev) hipEventDestroy(ev);
@@ -1504,6 +1547,45 @@ int64_t dint_log_drain_device(dint_engine_t *e, void *d_records, uint64_t cap, u
   return log_drain_locked(e, d_records, cap, lost, true, stream ? (hipStream_t)stream : e->stream);
 }
 
+// one chunk of dint_log_apply_device: m <= e->replay.cap records at d_rec, everything enqueued on st; the acks are counted
+// into e->replay.counts.  timed: the stream is drained and the stage times are added to stage_ms[0..2]
+int replay_chunk(dint_engine *e, const void *d_rec, uint32_t m, hipStream_t st, bool timed, double *stage_ms) {
+  const uint32_t wl = e->cfg.workload;
+  const dint_replay_scratch &r = e->replay;
+  if (timed) HIP_TRY(hipEventRecord(e->ev_replay[0], st));
+  if (wl == DINT_WL_TATP) {
+    // (the sort's temporary storage was sized for a full chunk; a shorter last chunk never needs more)
+    if (dint_replay_sort_bytes(m, st) > (int64_t)r.sort_tmp_bytes) return fail(DINT_EHIP, "radix sort: temporary storage too small");
+    if (!dint_launch_replay_group(d_rec, m, r, st)) return fail(DINT_EHIP, "radix sort failed");
+    if (timed) HIP_TRY(hipEventRecord(e->ev_replay[1], st));
+    // the READs, answered in place: one segment whose live count is the word k_replay_probe counted in
+    const uint32_t seg_cap = std::max(m, 2u);
+    if (int rc = run_pass(e, r.probe, seg_cap, r.probe, st, 0, dint_seg_view(1, seg_cap, (uint64_t)seg_cap * e->msg_size, r.probe_n, 0)))
+      return rc;
+    e->batches--;  // (not the caller's requests)
+    e->requests -= seg_cap;
+    dint_launch_replay_emit(d_rec, m, r, st);
+  } else {
+    if (timed) HIP_TRY(hipEventRecord(e->ev_replay[1], st));
+    dint_launch_replay_emit_sb(d_rec, m, r, st);
+  }
+  if (timed) HIP_TRY(hipEventRecord(e->ev_replay[2], st));
+  if (int rc = run_pass(e, r.msgs, m, r.msgs, st)) return rc;
+  dint_launch_replay_count(wl, m, r, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
+  if (timed) {
+    HIP_TRY(hipEventRecord(e->ev_replay[3], st));
+    HIP_TRY(hipEventSynchronize(e->ev_replay[3]));
+    for (int k = 0; k < 3; k++) {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, e->ev_replay[k], e->ev_replay[k + 1]));
+      stage_ms[k] += ms;
+    }
+  }
+  return 0;
+}
+
 int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t chunk, dint_apply_stats *out) {
   if (!e || (n && !d_records)) return fail(DINT_EINVAL, "null argument");
   const uint32_t wl = e->cfg.workload;
@@ -1530,38 +1612,7 @@ int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, u
   const uint8_t *rec = (const uint8_t *)d_records;
   for (uint64_t off = 0; off < n; off += chunk, chunks++) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
-    const void *d_rec = rec + off * 64;
-    if (timed) HIP_TRY(hipEventRecord(e->ev_replay[0], st));
-    if (wl == DINT_WL_TATP) {
-      // (the sort's temporary storage was sized for a full chunk; a shorter last chunk never needs more)
-      if (dint_replay_sort_bytes(m, st) > (int64_t)r.sort_tmp_bytes) return fail(DINT_EHIP, "radix sort: temporary storage too small");
-      if (!dint_launch_replay_group(d_rec, m, r, st)) return fail(DINT_EHIP, "radix sort failed");
-      if (timed) HIP_TRY(hipEventRecord(e->ev_replay[1], st));
-      // the READs, answered in place: one segment whose live count is the word k_replay_probe counted in
-      const uint32_t seg_cap = std::max(m, 2u);
-      if (int rc = run_pass(e, r.probe, seg_cap, r.probe, st, 0, dint_seg_view(1, seg_cap, (uint64_t)seg_cap * e->msg_size, r.probe_n, 0)))
-        return rc;
-      e->batches--;  // (not the caller's requests)
-      e->requests -= seg_cap;
-      dint_launch_replay_emit(d_rec, m, r, st);
-    } else {
-      if (timed) HIP_TRY(hipEventRecord(e->ev_replay[1], st));
-      dint_launch_replay_emit_sb(d_rec, m, r, st);
-    }
-    if (timed) HIP_TRY(hipEventRecord(e->ev_replay[2], st));
-    if (int rc = run_pass(e, r.msgs, m, r.msgs, st)) return rc;
-    dint_launch_replay_count(wl, m, r, st);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
-    if (timed) {
-      HIP_TRY(hipEventRecord(e->ev_replay[3], st));
-      HIP_TRY(hipEventSynchronize(e->ev_replay[3]));
-      for (int k = 0; k < 3; k++) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e->ev_replay[k], e->ev_replay[k + 1]));
-        stage_ms[k] += ms;
-      }
-    }
+    if (int rc = replay_chunk(e, rec + off * 64, m, st, timed, stage_ms)) return rc;
   }
   if (!out) return 0;
   HIP_TRY(hipStreamSynchronize(st));
@@ -1571,6 +1622,100 @@ int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, u
   out->applied = c[0] + c[1] + c[2];
   out->chunks = chunks;
   for (int k = 0; k < 3; k++) out->reserved[k] = (uint64_t)(stage_ms[k] * 1e6);
+  return 0;
+}
+
+int dint_log_apply_folded_device(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t chunk, uint32_t flags,
+                                 dint_fold_stats *out) {
+  if (!e || (n && !d_records)) return fail(DINT_EINVAL, "null argument");
+  if (flags & ~DINT_FOLD_DRY_RUN) return fail(DINT_EINVAL, "unknown flags %#x", flags);
+  if ((uintptr_t)d_records & 15) return fail(DINT_EINVAL, "records: 16-byte aligned");
+  const uint32_t wl = e->cfg.workload;
+  if (wl != DINT_WL_TATP && wl != DINT_WL_SMALLBANK) return fail(DINT_ESTATE, "workload has no table a log replays into");
+  if (e->shard.count > 1) return fail(DINT_EINVAL, "a sharded engine: the log would have to be routed first");
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = ahead_settle(e)) return rc;
+  if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
+  HIP_TRY(hipSetDevice(e->device));
+  if (chunk == 0 || chunk > e->pass_max) chunk = e->pass_max;
+  if (out) memset(out, 0, sizeof *out);
+  if (n == 0) return 0;
+  const bool dry = (flags & DINT_FOLD_DRY_RUN) != 0;
+  const uint32_t cap = (uint32_t)std::min<uint64_t>(chunk, n);
+  if (int rc = fold_alloc(e, cap)) return rc;
+  if (!dry) {
+    if (int rc = replay_alloc(e, cap)) return rc;  // (the deferred records of a chunk: never more than the chunk)
+    if (int rc = state_alloc(e, false)) return rc;
+  }
+  const dint_fold_scratch &f = e->fold;
+  hipStream_t st = e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  HIP_TRY(hipMemsetAsync(f.counts, 0, DINT_FOLD_COUNTS * sizeof(unsigned long long), st));
+  if (!dry) HIP_TRY(hipMemsetAsync(e->replay.counts, 0, 4 * sizeof(unsigned long long), st));
+  const bool timed = e->timer.on && out;
+  if (timed)
+    for (hipEvent_t &ev : e->ev_fold)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  double ms4[4] = {0, 0, 0, 0};
+  uint64_t chunks = 0;
+  const uint8_t *rec = (const uint8_t *)d_records;
+  for (uint64_t off = 0; off < n; off += chunk, chunks++) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - off);
+    const void *d_rec = rec + off * 64;
+    if (timed) HIP_TRY(hipEventRecord(e->ev_fold[0], st));
+    if (!dint_launch_fold(d_rec, m, wl, e->kv.d_dev, f, st, timed ? e->ev_fold[1] : nullptr)) return fail(DINT_EHIP, "log fold: a sort or scan failed");
+    if (int rc = state_launched()) return rc;
+    uint32_t w[4];  // {deferred records, repair records, rows}
+    HIP_TRY(hipMemcpyAsync(w, f.words, sizeof w, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the chunk's one wait for its counts
+    if (w[0] > m || w[1] > m) return fail(DINT_EHIP, "log fold: counts beyond the chunk");
+    if (timed) HIP_TRY(hipEventRecord(e->ev_fold[2], st));
+    if (!dry && w[1]) {
+      e->blank = false;
+      // The fold wrote these records in ascending (table, bucket) order and names no table the workload has not, so the order
+      // check cannot fail; its flag is collected with the repair's counts and read once, at the end of the call.
+      dint_launch_state_repair_check(e->kv, f.repair, w[1], e->state, st);
+      dint_launch_fold_rotate(e->kv.d_dev, st);
+      // (the pend set: as dint_state_repair chooses it)
+      dint_launch_state_repair(e->kv, f.repair, w[1], (uint32_t)(e->scratch.kvs.pass_no & 1), e->scratch.stats, e->state, st);
+      dint_launch_fold_harvest(e->state.words + 8, f, st);
+      if (int rc = state_launched()) return rc;
+    }
+    if (timed) HIP_TRY(hipEventRecord(e->ev_fold[3], st));
+    if (!dry && w[0])
+      if (int rc = replay_chunk(e, f.def_rec, w[0], st, false, nullptr)) return rc;
+    if (timed) {
+      HIP_TRY(hipEventRecord(e->ev_fold[4], st));
+      HIP_TRY(hipEventSynchronize(e->ev_fold[4]));
+      for (int k = 0; k < 4; k++) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e->ev_fold[k], e->ev_fold[k + 1]));
+        ms4[k] += ms;
+      }
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  unsigned long long c[DINT_FOLD_COUNTS], a[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpy(c, f.counts, sizeof c, hipMemcpyDeviceToHost));
+  if (!dry) HIP_TRY(hipMemcpy(a, e->replay.counts, sizeof a, hipMemcpyDeviceToHost));
+  if (out) {
+    // folded records: what they would have been; deferred ones: what the replica acked (a dry run: what they would be)
+    out->commits = c[0] + (dry ? c[3] : a[0]); out->inserts = c[1] + (dry ? c[4] : a[1]); out->deletes = c[2] + (dry ? c[5] : a[2]);
+    out->applied = out->commits + out->inserts + out->deletes;
+    out->chunks = chunks;
+    out->rows = c[8]; out->deferred_records = c[6]; out->folded_records = n - c[6]; out->deferred_buckets = c[7];
+    out->repair_records = c[9];
+    out->updated = c[10]; out->inserted = c[11]; out->deleted = c[12]; out->refused = c[13];
+    for (int k = 0; k < 4; k++) out->ns[k] = (uint64_t)(ms4[k] * 1e6);
+  }
+  if (c[14]) return fail(DINT_EHIP, "log fold: repair records out of bucket order (an internal error)");
+  if (c[13]) {
+    // reported here, as dint_state_repair does: the host path's own check (dint_wait) must not report these inserts a second time
+    e->pool_seen += c[13];
+    *e->h_pool += c[13];
+    if (e->h_pool[1] < e->pool_seen) e->h_pool[1] = e->pool_seen;
+    return fail(DINT_ENOMEM, "%llu inserts found the overflow-entry pool full (dint_config.pool_entries); the other records were applied", c[13]);
+  }
   return 0;
 }
 

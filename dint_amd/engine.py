@@ -209,6 +209,20 @@ class Engine:
         d["stage_ns"] = dict(zip(("group", "probe", "apply"), s.reserved))
         return d
 
+    def log_apply_folded(self, d_records, n: int, chunk: int = 0, dry_run: bool = False) -> dict:
+        """dint_log_apply_folded_device: log_apply_device with every chunk folded first -- the records of a row collapse to its
+        last value and the version their count gives (csrc/log_fold.h), written by the state repair's kernel; only the records of
+        buckets that hold a touched key twice go through the serial replay.  Leaves the rows log_apply_device leaves.  Returns
+        the counts (as log_apply_device's, then rows / folded_records / deferred_records / deferred_buckets / repair_records /
+        updated / inserted / deleted / refused) and stage_ns (with timing_enable on).  dry_run=True writes no table byte.
+        Raises DintError (DINT_ENOMEM) after applying the rest when inserts found the overflow pool full; `last_fold` holds
+        the counts also then."""
+        s = _lib.FoldStats()
+        rc = self._L.dint_log_apply_folded_device(self._h, _ptr(d_records), n, chunk, _lib.FOLD_DRY_RUN if dry_run else 0, C.byref(s))
+        self.last_fold = s.as_dict()
+        _lib.check(rc)
+        return self.last_fold
+
     # ---- state sync (dint_state_digest / dint_state_diff / dint_state_repair) ----------------------------
     def state_digest(self, stream: int = 0) -> list:
         """dint_state_digest: per table {rows, sum, xr} over the valid rows -- the row count, and the sum mod 2^64 and the

@@ -91,6 +91,45 @@ def apply_log_device(engine, d_records, n: int, chunk: int = 0) -> dict:
     return {"applied": n, "commits": st["commits"], "inserts": st["inserts"], "deletes": st["deletes"]}
 
 
+def apply_log_folded(engine, d_records, n: int, chunk: int = 0) -> dict:
+    """apply_log_device through the fold (Engine.log_apply_folded; csrc/k_fold.hip, csrc/log_fold.h): the same rows afterwards,
+    the same keys with the same counts, plus `folded` and `deferred` -- the records whose row's net effect the state repair wrote,
+    and the ones that went through the serial replay."""
+    if n == 0:
+        return {"applied": 0}
+    st = engine.log_apply_folded(d_records, n, chunk)
+    if engine.workload == Workload.SMALLBANK:
+        out = {"applied": n, "acks": st["commits"]}
+    else:
+        out = {"applied": n, "commits": st["commits"], "inserts": st["inserts"], "deletes": st["deletes"]}
+    out["folded"], out["deferred"] = st["folded_records"], st["deferred_records"]
+    return out
+
+
+def fold_log_host(workload, hash_size, dumps, records) -> tuple:
+    """dint_log_fold_host (include/dint_driver.h): ONE chunk of records folded on the host against dumped rows.  dumps[t] = (keys,
+    vers, ...) of table t as Engine.dump_rows returns them; hash_size[t] = the table's bucket count.  Returns
+    (deferred flags per record, repair records as a LOG_REC array, stats).  No device call."""
+    import ctypes as C
+
+    from . import _lib
+
+    records = np.ascontiguousarray(records)
+    nt = len(dumps)
+    off = np.zeros(nt + 1, "<u8")
+    off[1:] = np.cumsum([len(d[0]) for d in dumps])
+    keys = np.ascontiguousarray(np.concatenate([np.asarray(d[0], "<u8") for d in dumps]), "<u8")
+    vers = np.ascontiguousarray(np.concatenate([np.asarray(d[1], "<u4") for d in dumps]), "<u4")
+    hs = np.ascontiguousarray(hash_size, "<u8")
+    n = len(records)
+    deferred = np.zeros(max(n, 1), np.uint8)
+    repair = np.zeros(max(n, 1), LOG_REC)
+    s = _lib.FoldStats()
+    got = _lib.check(_lib.load().dint_log_fold_host(int(workload), nt, hs.ctypes.data, off.ctypes.data, keys.ctypes.data, vers.ctypes.data,
+                                                    records.ctypes.data, n, deferred.ctypes.data, repair.ctypes.data, n, C.byref(s)))
+    return deferred[:n].astype(bool), repair[:got], s.as_dict()
+
+
 def digests_equal(a, b) -> bool:
     """do the two engines hold the same rows (keys, versions, values), whatever their chains look like?"""
     return a.state_digest() == b.state_digest()
@@ -419,7 +458,7 @@ class LogShipper:
     with resync_on_loss=True `step()` does so by itself when it finds records lost.  The caller keeps both engines quiet
     for the duration of a resync (no submissions to either)."""
 
-    def __init__(self, primary, replica, cap: int = 1 << 20, chunk: int = 0, resync_on_loss: bool = False):
+    def __init__(self, primary, replica, cap: int = 1 << 20, chunk: int = 0, resync_on_loss: bool = False, fold: bool = False):
         import torch
 
         assert primary.workload == replica.workload
@@ -427,6 +466,7 @@ class LogShipper:
         self.buf = torch.empty(cap * LOG_REC.itemsize, dtype=torch.uint8, device="cuda")
         self.shipped = self.lost = self.resyncs = 0
         self.resync_on_loss = resync_on_loss
+        self.fold = fold  # replay through apply_log_folded: step() then adds `folded` and `deferred`
 
     def step(self) -> dict:
         n, lost = self.primary.log_drain_device(self.buf, self.cap)
@@ -434,7 +474,7 @@ class LogShipper:
             # the drained records are part of what the primary's tables already hold: dropped, not replayed
             self.lost += lost
             return {"applied": 0, "lost": lost, "resync": self.resync()}
-        out = apply_log_device(self.replica, self.buf, n, self.chunk)
+        out = (apply_log_folded if self.fold else apply_log_device)(self.replica, self.buf, n, self.chunk)
         out["lost"] = lost
         self.shipped += n
         self.lost += lost

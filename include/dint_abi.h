@@ -295,6 +295,44 @@ typedef struct dint_apply_stats {
  * dint_submit_device_ahead still pending (DINT_ESTATE, as dint_snapshot).  The replica's own log is not appended to (backup
  * operations never are).  Scratch of ~200 bytes per record of a chunk is allocated on the first call and kept. */
 int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t chunk, dint_apply_stats *out);
+
+#define DINT_FOLD_DRY_RUN 1u
+typedef struct dint_fold_stats {
+  uint64_t applied, commits, inserts, deletes, chunks; /* as dint_apply_stats: what the records would have been as backup operations */
+  uint64_t rows;             /* distinct (table, key) per chunk, summed over the chunks */
+  uint64_t folded_records;   /* records whose row's net effect went to the repair */
+  uint64_t deferred_records; /* records that went through the serial replay (dint_log_apply_device's chunk routine) */
+  uint64_t deferred_buckets; /* buckets that made them do so, per chunk, summed */
+  uint64_t repair_records, updated, inserted, deleted, refused; /* what reached the repair kernel and what it did (dint_repair_stats) */
+  uint64_t ns[4];  /* with dint_timing_enable: nanoseconds of [0] the key pass and the sorts, [1] probe, fold and emit, [2] the repair,
+                      [3] the deferred records' serial replay */
+  uint64_t reserved[5];
+} dint_fold_stats;
+/* (v5, additive) dint_log_apply_device with every chunk FOLDED first: the records of a chunk are sorted by (table, bucket, key, log
+ * index), the replica's chain is probed once per row, and each row's records collapse to their net effect -- the last value and the
+ * version the count of commits gives, or "gone" -- which dint_state_repair's kernel writes with one lane per bucket; no hot-path pass
+ * sees those records.  The rule is dint_amd/csrc/log_fold.h.  Afterwards every table holds the multiset of rows (key, version, value)
+ * that dint_log_apply_device leaves on the same replica, records and chunk, so dint_state_digest is equal; chain layout, holes and
+ * pool use may differ ("state is rows only", below).  A bucket in which a row the chunk touches is held twice or more is DEFERRED:
+ * all its records of the chunk go through dint_log_apply_device's own chunk routine in log order (folded and deferred buckets are
+ * disjoint, so the two write paths commute).
+ * Contract, refusals and stream ordering are dint_log_apply_device's: lock / log / store engines DINT_ESTATE, a sharded engine
+ * DINT_EINVAL, an announced batch pending DINT_ESTATE, d_records == NULL with n > 0 DINT_EINVAL, n == 0 returns 0; flags other than
+ * DINT_FOLD_DRY_RUN and records not 16-byte aligned: DINT_EINVAL.  Keys stay below 2^60, as for the serial replay.  The records
+ * stay untouched; the replica's lock words, log ring and log cursor are left alone.  FOLDED records are not counted in the
+ * replica's request counters (dint_stats batches / requests; nor in missing_keys, which the serial replay bumps for a smallbank
+ * record of an absent row): only the deferred ones pass the hot path.  The call is synchronous: per chunk the host waits ONCE,
+ * to learn the deferred and repair record counts, and once more at the end of the call; it returns with `out` (may be NULL)
+ * filled.  DINT_FOLD_DRY_RUN fills every field except updated / inserted / deleted / refused and
+ * writes no table byte (a blank engine stays blank).
+ * Pool: the serial replay may need overflow entries only for a while; the fold never needs more than it: in front of every repair launch the
+ * pool's pend lists are rotated into its free lists, as a hot-path pass does, so entries a folded delete emptied are allocated
+ * again by later chunks and calls although no pass runs.  When an insert of the
+ * repair finds the pool full, equality with the unfolded path is not promised; it is reported as dint_state_repair reports it --
+ * `refused`, dint_stats.pool_exhausted, DINT_ENOMEM, the rest applied.  Scratch of ~250 bytes per record of a chunk is allocated on
+ * the first call and kept, beside dint_log_apply_device's own for the deferred records. */
+int dint_log_apply_folded_device(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t chunk, uint32_t flags,
+                                 dint_fold_stats *out);
 /* ---- state sync (v5, additive): is a replica equal to its primary, what differs, and the repair -- on the device ----------
  * "State" is ROWS ONLY: per table the multiset of valid (key, ver, val) slots.  Lock words, the log ring, the pool's free
  * lists and the chain layout are per server and transient; a replica rebuilt from a log has other chains than its primary.

@@ -180,6 +180,20 @@ int dint_lock_gclient_get_stats(dint_lock_gclient_t *c, dint_fasst_client_stats 
  * choose (COMMIT_BCK 13 / INSERT_BCK 19 / DELETE_BCK 23).  No device call. */
 int dint_log_classify_host(const void *records, uint64_t n, const uint8_t *exists0, uint8_t *types_out);
 
+/* ---- log fold: the rule on the host (dint_amd/csrc/log_fold.h) ---------------------------------------------------
+ * What dint_log_apply_folded_device (include/dint_abi.h) decides for ONE chunk, restated over dumped rows for tests and tools:
+ * workload = DINT_WL_TATP / DINT_WL_SMALLBANK with n_tables tables of hash_size[t] buckets (dint_hash_size); the replica's rows as
+ * dint_dump_rows returns them, table after table: keys / vers [row_off[t] .. row_off[t + 1]) are table t's (dump order is chain
+ * order inside a bucket: the first row of a key is the visible one); records = the chunk's n canonical 64-byte log records in
+ * log order.  deferred_out[i] = record i goes through the serial replay; repair_out = the repair records in the device call's
+ * order, room for cap; out (may be NULL) = applied / commits / inserts / deletes / chunks (1) / rows / folded_records /
+ * deferred_records / deferred_buckets / repair_records, the rest zero.  Returns the records written (<= cap; out->repair_records
+ * says how many there are), or DINT_EINVAL / DINT_ENOMEM.  No device call. */
+struct dint_fold_stats; /* include/dint_abi.h */
+int64_t dint_log_fold_host(uint32_t workload, uint32_t n_tables, const uint64_t *hash_size, const uint64_t *row_off,
+                           const uint64_t *keys, const uint32_t *vers, const void *records, uint64_t n, uint8_t *deferred_out,
+                           void *repair_out, uint64_t cap, struct dint_fold_stats *out);
+
 /* ---- state sync: the rules on the host (dint_amd/csrc/state_sync.h) ------------------------------------------
  * What dint_state_digest / dint_state_diff (include/dint_abi.h) compute on the GPU, restated over dumped rows
  * (dint_dump_rows: keys, versions, values of val_size = 40 or 8 bytes) for tests and tools.  No device call.

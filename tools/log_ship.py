@@ -2,7 +2,7 @@
 """Replay one primary's log into two fresh replicas -- once over the host (dint_log_drain + recovery.apply_log), once
 without leaving the GPU (dint_log_drain_device + dint_log_apply_device) -- and say what each costs.
 
-    tools/log_ship.py [--workload tatp|smallbank] [--rows N] [--records M] [--chunk C] [--timeout S]
+    tools/log_ship.py [--workload tatp|smallbank] [--rows N] [--records M] [--chunk C] [--timeout S] [--fold]
 
 A primary takes M committed writes (the log record, then the primary operation, as tests/test_ebpf_surface.py
 _committed_writes sends them; rows drawn Zipf-0.8: updates, and for tatp one delete in four and inserts of rows that are
@@ -10,6 +10,14 @@ gone).  Its log is then replayed twice from the same cursor (snapshot / restore 
 of both paths (drain + replay, wall clock, replies complete), the device path split by stage (HIP events on the replica's
 stream, in a run of its own: dint_timing_enable drains the stream chunk by chunk), and whether both replicas' rows equal
 the primary's.  The device path is run once before it is timed (kernel load, scratch allocation).
+
+--fold measures the folded replay (dint_log_apply_folded_device) against the unfolded one instead: the same drained log into ONE
+replica, put back by restore before every run, the two paths alternating; printed are the median and range of 7 runs of each between
+HIP events after a warm one, the fold's stage times (one more run with dint_timing_enable: sort, fold, repair, deferred), its
+deferred_records, and whether the digests of the two paths' end states are equal.  Both calls are synchronous, and the events are
+recorded on torch's current stream, not the engine's own: a figure is the time between two synchronised points around the call
+(queueing, the kernels, the per-chunk wait), not device time on the stream that did the work; the stage times are the engine's own
+events on its stream.
 
 All GPU work happens in ONE child process under a time limit; the parent never opens the GPU."""
 import argparse
@@ -67,11 +75,11 @@ def writes(rng, rows, live, n, tatp):
     return m
 
 
-def child(a):
+def primary_with_log(a):
+    """a primary that has taken a.records committed writes and been snapshotted: (prim, fresh, same, tatp)"""
     import numpy as np
-    import torch
 
-    from dint_amd import recovery, wire
+    from dint_amd import wire
     from dint_amd.engine import Engine
 
     tatp = a.workload == "tatp"
@@ -111,6 +119,58 @@ def child(a):
         left -= n
     assert prim.stats()["missing_keys"] == 0, "the generator sent a write to a row that is not there"
     prim.snapshot()
+    return prim, fresh, same, tatp
+
+
+def child_fold(a):
+    import statistics
+
+    import torch
+
+    prim, fresh, _, _ = primary_with_log(a)
+    buf = torch.empty(a.records * 64, dtype=torch.uint8, device="cuda")
+    assert prim.log_drain_device(buf, a.records) == (a.records, 0)
+    rep = fresh()
+    rep.snapshot()
+    paths = {"folded": lambda: rep.log_apply_folded(buf, a.records, a.chunk), "unfolded": lambda: rep.log_apply_device(buf, a.records, a.chunk)}
+    ms, last, digest = {k: [] for k in paths}, {}, {}
+    for run in range(8):  # a warm run of each, then 7 timed, the two paths alternating
+        for name, call in paths.items():
+            rep.restore()
+            torch.cuda.synchronize()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            last[name] = call()
+            ev[1].record()
+            torch.cuda.synchronize()
+            if run:
+                ms[name].append(ev[0].elapsed_time(ev[1]))
+            digest[name] = rep.state_digest()
+    rep.restore()
+    rep.timing_enable(True)
+    staged = rep.log_apply_folded(buf, a.records, a.chunk)
+    rep.timing_enable(False)
+    out = {"workload": a.workload, "rows": a.rows, "records": a.records, "chunk": a.chunk, "runs": 7}
+    for name, v in ms.items():
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "records_per_s": a.records / (statistics.median(v) / 1e3)}
+    out["ratio"] = out["unfolded"]["median_ms"] / out["folded"]["median_ms"]
+    out["stage_ms"] = {k: v / 1e6 for k, v in staged["stage_ns"].items()}
+    out["fold"] = {k: v for k, v in last["folded"].items() if k != "stage_ns"}
+    shared = ("applied", "commits", "inserts", "deletes", "chunks")
+    out["counts_equal"] = all(last["folded"][k] == last["unfolded"][k] for k in shared)
+    out["digests_equal"] = digest["folded"] == digest["unfolded"]
+    print(json.dumps(out))
+    return 0 if out["counts_equal"] and out["digests_equal"] else 1
+
+
+def child(a):
+    import numpy as np  # noqa: F401
+    import torch
+
+    from dint_amd import recovery
+
+    prim, fresh, same, tatp = primary_with_log(a)
     out = {"workload": a.workload, "rows": a.rows, "records": a.records, "chunk": a.chunk, "runs": "one run"}
 
     # ---- the host path
@@ -166,12 +226,13 @@ def main():
     ap.add_argument("--records", type=int, default=4_000_000)
     ap.add_argument("--chunk", type=int, default=0, help="records per replay pass (0 = the replica's max_pass)")
     ap.add_argument("--timeout", type=int, default=540, help="seconds the GPU child may take")
+    ap.add_argument("--fold", action="store_true", help="measure the folded replay against the unfolded one")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        return child(a)
+        return child_fold(a) if a.fold else child(a)
     cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", "--workload", a.workload,
-           "--rows", str(a.rows), "--records", str(a.records), "--chunk", str(a.chunk)]
+           "--rows", str(a.rows), "--records", str(a.records), "--chunk", str(a.chunk)] + (["--fold"] if a.fold else [])
     return subprocess.run(cmd).returncode  # (124 / 137: the time limit; nothing else is started after a failure)
 
 

@@ -29,6 +29,7 @@ SYMBOLS = [
     "dint_log_drain_device", "dint_log_apply_device", "dint_log_apply_folded_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
     "dint_state_export", "dint_state_import", "dint_state_rehash", "dint_state_stats",
     "dint_state_verify", "dint_state_compact",
+    "dint_state_block_digest", "dint_state_block_select", "dint_state_block_rows", "dint_state_block_diff",
 ]
 #: dint_log_apply_folded_device flags
 FOLD_DRY_RUN = 1
@@ -94,6 +95,21 @@ class DiffStats(C.Structure):
     """dint_diff_stats (include/dint_abi.h)"""
     _fields_ = [("total", C.c_uint64), ("only_a", C.c_uint64), ("only_b", C.c_uint64), ("val_differs", C.c_uint64),
                 ("ver_only", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class BlockDigest(C.Structure):
+    """dint_block_digest (include/dint_abi.h)"""
+    _fields_ = [("rows", C.c_uint64), ("sum", C.c_uint64), ("xr", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class BlockStats(C.Structure):
+    """dint_block_stats (include/dint_abi.h)"""
+    _fields_ = [("total", C.c_uint64), ("n_blocks", C.c_uint32), ("n_tables", C.c_uint32), ("blocks", C.c_uint32 * 5),
+                ("block_buckets", C.c_uint32), ("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self) -> dict:
+        return {"total": self.total, "n_blocks": self.n_blocks, "block_buckets": self.block_buckets,
+                "blocks": list(self.blocks)[:self.n_tables]}
 
 
 class RepairStats(C.Structure):
@@ -245,6 +261,10 @@ def load() -> C.CDLL:
         "dint_state_digest": (C.c_int, [vp, C.POINTER(TableDigest), u32, vp]),
         "dint_state_diff": (i64, [vp, vp, vp, u64, C.POINTER(DiffStats), vp]),
         "dint_state_repair": (C.c_int, [vp, vp, u64, C.POINTER(RepairStats), vp]),
+        "dint_state_block_digest": (i64, [vp, u64, vp, u64, C.POINTER(BlockStats), vp]),
+        "dint_state_block_select": (i64, [vp, vp, u32, vp, u64, vp]),
+        "dint_state_block_rows": (i64, [vp, u64, vp, u32, vp, u64, C.POINTER(BlockStats), vp]),
+        "dint_state_block_diff": (i64, [vp, u64, vp, u32, vp, u64, vp, u64, C.POINTER(DiffStats), vp]),
         "dint_state_export": (C.c_int, [vp, u32, u32, vp, u64, C.POINTER(ImageStats), vp]),
         "dint_state_import": (C.c_int, [vp, vp, u64, C.POINTER(ImageStats), vp]),
         "dint_state_rehash": (C.c_int, [vp, C.POINTER(vp), u32, u32, C.POINTER(RehashStats), vp]),
@@ -268,6 +288,10 @@ def load() -> C.CDLL:
         # ... and the compaction's rule (csrc/state_compact.h) over the same views
         "dint_state_compact_view_host": (C.c_int, [C.POINTER(TablesView), C.POINTER(TableCompact), u32, u32]),
         "dint_state_compact_view": (C.c_int, [i32, C.POINTER(TablesView), C.POINTER(TableCompact), u32, u32, vp]),
+        # ... and the block sync's rule (csrc/state_block.h) over the same views in host memory
+        "dint_state_block_digest_host": (i64, [C.POINTER(TablesView), u64, vp, u64, C.POINTER(BlockStats)]),
+        "dint_state_block_rows_host": (i64, [C.POINTER(TablesView), u64, vp, u32, vp, u64, C.POINTER(BlockStats)]),
+        "dint_state_block_diff_host": (i64, [C.POINTER(TablesView), u64, vp, u32, vp, u64, vp, u64, C.POINTER(DiffStats)]),
         # ... and the rehash's layout rule (csrc/state_rehash.h) over keys in source order
         "dint_state_rehash_place_host": (i64, [vp, u64, u64, u32, u32, vp, vp, vp]),
     }

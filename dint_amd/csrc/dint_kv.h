@@ -6,6 +6,7 @@
 
 #include "dint_kernels.h"
 #include "dint_kv_core.h"
+#include "state_block.h"
 #include "state_image.h"
 
 #define DINT_KV_MAX_TABLES 5
@@ -208,6 +209,42 @@ void dint_compact_free(dint_compact_scratch &s);
 struct dint_table_compact;
 int dint_compact_run(const dint_kv &kv, dint_verify_scratch vs, dint_compact_scratch &s, uint32_t flags, hipStream_t st,
                      struct dint_table_compact *out, hipEvent_t *ev);
+
+// ---- block sync (k_block.hip; state_block.h): digests per block of buckets, the blocks that differ, their rows, their diff --------
+struct dint_block_scratch {
+  unsigned long long *words = nullptr;  // [DINT_BLOCK_WORDS] device words: [0..3] the diff's records by kind, [DINT_BLOCK_TOTAL_AT] the records,
+                                        // [DINT_BLOCK_LANES_AT] the buckets of the listed blocks, [DINT_BLOCK_BAD_AT] (u32) state_block.h BK_BAD_*
+  unsigned long long *part = nullptr;   // [part_n][4] the digest's partial per chunk of 64 buckets, all tables in table order
+  uint64_t part_n = 0;
+  uint32_t *id_cnt = nullptr;           // [id_n] buckets of every listed block ...
+  uint64_t *id_off = nullptr;           // ... their exclusive scan: a listed block's first lane
+  uint64_t id_n = 0;
+  uint32_t *blk_cnt = nullptr;          // [blk_n] records per workgroup of 256 lanes ...
+  uint64_t *blk_off = nullptr;          // ... their exclusive scan
+  uint64_t blk_n = 0;
+  uint32_t *run_lo = nullptr, *run_hi = nullptr;  // [run_n] the diff: per lane its bucket's run [lo, hi) in the row list
+  uint64_t run_n = 0;
+};
+#define DINT_BLOCK_WORDS 8u
+#define DINT_BLOCK_TOTAL_AT 4u
+#define DINT_BLOCK_LANES_AT 5u
+#define DINT_BLOCK_BAD_AT 6u
+struct dint_block_stats;
+bool dint_block_geom(const dint_kv &kv, uint64_t block_buckets, bk_geom *g);  // false: not a block size
+uint64_t dint_block_chunks(const dint_kv &kv);
+void dint_block_fill_stats(dint_block_stats *out, const bk_geom &g, uint64_t total);
+// bk_blocks(g) digests into d_out (s.part: dint_block_chunks(kv) partials, not used for blocks of 64)
+void dint_launch_block_digest(const dint_kv &kv, const bk_geom &g, dint_block_scratch s, void *d_out, hipStream_t st);
+// n_ids > 0; lanes = an upper bound of the listed blocks' buckets the scratch is sized for (id arrays n_ids, blk arrays lanes / 256
+// rounded up, run arrays lanes).  The checks' findings and the totals into s.words ...
+void dint_launch_block_rows_count(const dint_kv &kv, const bk_geom &g, const void *d_ids, uint32_t n_ids, uint64_t lanes, dint_block_scratch s, hipStream_t st);
+// ... then (same stream, the host has seen no finding) the first `cap` records
+void dint_launch_block_rows_write(const dint_kv &kv, const bk_geom &g, const void *d_ids, uint32_t n_ids, uint64_t lanes, dint_block_scratch s, void *d_records,
+                                  uint64_t cap, hipStream_t st);
+void dint_launch_block_diff_count(const dint_kv &kv, const bk_geom &g, const void *d_ids, uint32_t n_ids, uint64_t lanes, const void *d_rows, uint32_t n_rows,
+                                  dint_block_scratch s, hipStream_t st);
+void dint_launch_block_diff_write(const dint_kv &kv, const bk_geom &g, const void *d_ids, uint32_t n_ids, uint64_t lanes, const void *d_rows, uint32_t n_rows,
+                                  dint_block_scratch s, void *d_records, uint64_t cap, hipStream_t st);
 
 // ---- state image (k_image.hip; state_image.h): the tables written out for another shard layout and read back --------
 struct dint_image_scratch {

@@ -139,6 +139,9 @@ struct dint_engine {
   // state sync (dint_state_digest / dint_state_diff / dint_state_repair): result words, and -- for the diff, in engine a --
   // the per-workgroup counts; allocated on first use
   dint_state_scratch state{};
+  // block sync (dint_state_block_digest / _rows / _diff): result words, the digest's partials, the id list's and the lanes' arrays;
+  // allocated on first use, grown to what a call needs and kept
+  dint_block_scratch block{};
   // table report (dint_state_stats): the workgroups' partial reports and the tables' reports, allocated on the first call
   dint_stats_scratch tstats{};
   // table verify (dint_state_verify): the owner words, partial reports and reclaim arrays, allocated on the first call and kept
@@ -640,6 +643,44 @@ int state_alloc(dint_engine *e, bool diff) {
   if (fresh) HIP_TRY(hipDeviceSynchronize());  // (the zero fills ran on the null stream: the engine's stream does not wait for it)
   return 0;
 }
+// block sync scratch: every array grows to what a call needs and is kept (no zero fill: every call clears what it reads)
+void block_free(dint_engine *e) {
+  dint_block_scratch &s = e->block;
+  hipFree(s.words); hipFree(s.part); hipFree(s.id_cnt); hipFree(s.id_off); hipFree(s.blk_cnt); hipFree(s.blk_off); hipFree(s.run_lo); hipFree(s.run_hi);
+  s = dint_block_scratch{};
+}
+int block_reserve(dint_engine *e, uint64_t chunks, uint64_t ids, uint64_t lanes, bool runs) {
+  dint_block_scratch &s = e->block;
+  auto grow = [](void **a, size_t sa, void **b, size_t sb, uint64_t &have, uint64_t need) -> int {
+    if (need <= have) return 0;
+    hipFree(*a); hipFree(*b);
+    *a = *b = nullptr;
+    have = 0;
+    int rc = dev_alloc(a, (size_t)need * sa, false);
+    if (!rc) rc = dev_alloc(b, (size_t)need * sb, false);
+    if (rc) {
+      hipFree(*a); hipFree(*b);
+      *a = *b = nullptr;
+      return rc;
+    }
+    have = need;
+    return 0;
+  };
+  if (!s.words)
+    if (int rc = dev_alloc((void **)&s.words, DINT_BLOCK_WORDS * sizeof(unsigned long long), false)) return rc;
+  if (chunks > s.part_n) {
+    hipFree(s.part);
+    s.part = nullptr;
+    s.part_n = 0;
+    if (int rc = dev_alloc((void **)&s.part, (size_t)chunks * 4 * sizeof(unsigned long long), false)) return rc;
+    s.part_n = chunks;
+  }
+  if (int rc = grow((void **)&s.id_cnt, sizeof(uint32_t), (void **)&s.id_off, sizeof(uint64_t), s.id_n, ids)) return rc;
+  if (int rc = grow((void **)&s.blk_cnt, sizeof(uint32_t), (void **)&s.blk_off, sizeof(uint64_t), s.blk_n, (lanes + 255) / 256)) return rc;
+  if (runs)
+    if (int rc = grow((void **)&s.run_lo, sizeof(uint32_t), (void **)&s.run_hi, sizeof(uint32_t), s.run_n, lanes)) return rc;
+  return 0;
+}
 // the checks the three state calls share for one engine, before any GPU work
 int state_check(const dint_engine *e, bool sharded_ok) {
   if (!e->kv.n_tables) return fail(DINT_ESTATE, "workload has no kv table");
@@ -986,6 +1027,7 @@ void dint_engine_destroy(dint_engine_t *e) {
   replay_free(e);
   fold_free(e);
   state_free(e);
+  block_free(e);
   hipFree(e->tstats.part); hipFree(e->tstats.out);
   e->tstats = dint_stats_scratch{};
   dint_verify_free(e->tverify);
@@ -1870,6 +1912,116 @@ int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uin
     out->total = h[4]; out->only_a = h[0]; out->only_b = h[1]; out->val_differs = h[2]; out->ver_only = h[3];
   }
   return (int64_t)std::min<uint64_t>(h[4], d_records ? cap : 0);
+}
+
+// ---- block sync (k_block.hip; state_block.h) ----------------------------------------------------------------------------------
+namespace {
+// an upper bound of the buckets n_ids listed blocks hold: tight for a good list (only a table's last block is short)
+uint64_t block_lanes_max(const dint_kv &kv, const bk_geom &g, uint32_t n_ids) {
+  uint64_t all = 0;
+  for (uint32_t t = 0; t < kv.n_tables; t++) all += kv.h.tab[t].n_local;
+  return std::max<uint64_t>(1, std::min<uint64_t>(all, (uint64_t)n_ids << g.shift));
+}
+}  // namespace
+
+int64_t dint_state_block_digest(dint_engine_t *e, uint64_t block_buckets, void *d_out, uint64_t cap_blocks, dint_block_stats *out_stats, void *stream) {
+  if (!e) return fail(DINT_EINVAL, "null engine");
+  if (int rc = state_check(e, true)) return rc;
+  bk_geom g;
+  if (!dint_block_geom(e->kv, block_buckets, &g)) return fail(DINT_EINVAL, "block_buckets: a power of two, 64 .. 2^20");
+  if ((uintptr_t)d_out & 7) return fail(DINT_EINVAL, "the digests need an 8-byte aligned buffer");
+  if (d_out && cap_blocks < bk_blocks(g)) return fail(DINT_EINVAL, "%u blocks, room for %llu", bk_blocks(g), (unsigned long long)cap_blocks);
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  dint_block_fill_stats(out_stats, g, bk_blocks(g));
+  if (!d_out) return bk_blocks(g);
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = block_reserve(e, g.shift == 6 ? 0 : dint_block_chunks(e->kv), 0, 0, false)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  dint_launch_block_digest(e->kv, g, e->block, d_out, st);
+  if (int rc = state_launched()) return rc;
+  if (int rc = mark_stream(e, st)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));  // (the one synchronisation of the call)
+  return bk_blocks(g);
+}
+
+int64_t dint_state_block_rows(dint_engine_t *e, uint64_t block_buckets, const void *d_ids, uint32_t n_ids, void *d_records, uint64_t cap,
+                              dint_block_stats *out_stats, void *stream) {
+  if (!e) return fail(DINT_EINVAL, "null engine");
+  if (int rc = state_check(e, true)) return rc;
+  bk_geom g;
+  if (!dint_block_geom(e->kv, block_buckets, &g)) return fail(DINT_EINVAL, "block_buckets: a power of two, 64 .. 2^20");
+  if ((n_ids && !d_ids) || ((uintptr_t)d_ids & 3)) return fail(DINT_EINVAL, "n_ids ids need a 4-byte aligned buffer");
+  if ((cap && !d_records) || ((uintptr_t)d_records & 7)) return fail(DINT_EINVAL, "cap records need an 8-byte aligned buffer");
+  if (n_ids > bk_blocks(g)) return fail(DINT_EINVAL, "%u ids, %u blocks: %s", n_ids, bk_blocks(g), bk_bad_name(BK_BAD_IDS));
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  dint_block_fill_stats(out_stats, g, 0);
+  if (n_ids == 0) return 0;
+  HIP_TRY(hipSetDevice(e->device));
+  const uint64_t lanes = block_lanes_max(e->kv, g, n_ids);
+  if (int rc = block_reserve(e, 0, n_ids, lanes, false)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  dint_launch_block_rows_count(e->kv, g, d_ids, n_ids, lanes, e->block, st);
+  if (int rc = state_launched()) return rc;
+  unsigned long long h[DINT_BLOCK_WORDS];
+  HIP_TRY(hipMemcpyAsync(h, e->block.words, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint32_t bad = (uint32_t)h[DINT_BLOCK_BAD_AT];
+  if (!bad && h[DINT_BLOCK_TOTAL_AT] && d_records && cap) {
+    dint_launch_block_rows_write(e->kv, g, d_ids, n_ids, lanes, e->block, d_records, cap, st);
+    if (int rc = state_launched()) return rc;
+    if (int rc = mark_stream(e, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+  } else if (int rc = mark_stream(e, st)) {
+    return rc;
+  }
+  if (bad) return fail(DINT_EINVAL, "%s; nothing was written", bk_bad_name(bad));
+  if (out_stats) out_stats->total = h[DINT_BLOCK_TOTAL_AT];
+  return (int64_t)std::min<uint64_t>(h[DINT_BLOCK_TOTAL_AT], d_records ? cap : 0);
+}
+
+int64_t dint_state_block_diff(dint_engine_t *e, uint64_t block_buckets, const void *d_ids, uint32_t n_ids, const void *d_rows, uint64_t n_rows,
+                              void *d_records, uint64_t cap, dint_diff_stats *out_stats, void *stream) {
+  if (!e) return fail(DINT_EINVAL, "null engine");
+  if (int rc = state_check(e, true)) return rc;
+  bk_geom g;
+  if (!dint_block_geom(e->kv, block_buckets, &g)) return fail(DINT_EINVAL, "block_buckets: a power of two, 64 .. 2^20");
+  if ((n_ids && !d_ids) || ((uintptr_t)d_ids & 3)) return fail(DINT_EINVAL, "n_ids ids need a 4-byte aligned buffer");
+  if ((n_rows && !d_rows) || ((uintptr_t)d_rows & 7) || n_rows > BK_MAX_ROWS) return fail(DINT_EINVAL, "n_rows rows need an 8-byte aligned buffer; fewer than 2^32 - 16");
+  if ((cap && !d_records) || ((uintptr_t)d_records & 7)) return fail(DINT_EINVAL, "cap records need an 8-byte aligned buffer");
+  if (n_ids > bk_blocks(g)) return fail(DINT_EINVAL, "%u ids, %u blocks: %s", n_ids, bk_blocks(g), bk_bad_name(BK_BAD_IDS));
+  if (n_ids == 0 && n_rows) return fail(DINT_EINVAL, "%s; nothing was written", bk_bad_name(BK_BAD_HOME));
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  if (out_stats) memset(out_stats, 0, sizeof *out_stats);
+  if (n_ids == 0) return 0;
+  HIP_TRY(hipSetDevice(e->device));
+  const uint64_t lanes = block_lanes_max(e->kv, g, n_ids);
+  if (int rc = block_reserve(e, 0, n_ids, lanes, true)) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  dint_launch_block_diff_count(e->kv, g, d_ids, n_ids, lanes, d_rows, (uint32_t)n_rows, e->block, st);
+  if (int rc = state_launched()) return rc;
+  unsigned long long h[DINT_BLOCK_WORDS];
+  HIP_TRY(hipMemcpyAsync(h, e->block.words, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint32_t bad = (uint32_t)h[DINT_BLOCK_BAD_AT];
+  if (!bad && h[DINT_BLOCK_TOTAL_AT] && d_records && cap) {
+    dint_launch_block_diff_write(e->kv, g, d_ids, n_ids, lanes, d_rows, (uint32_t)n_rows, e->block, d_records, cap, st);
+    if (int rc = state_launched()) return rc;
+    if (int rc = mark_stream(e, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+  } else if (int rc = mark_stream(e, st)) {
+    return rc;
+  }
+  if (bad) return fail(DINT_EINVAL, "%s; nothing was written", bk_bad_name(bad));
+  if (out_stats) {
+    out_stats->total = h[DINT_BLOCK_TOTAL_AT]; out_stats->only_a = h[0]; out_stats->only_b = h[1]; out_stats->val_differs = h[2]; out_stats->ver_only = h[3];
+  }
+  return (int64_t)std::min<uint64_t>(h[DINT_BLOCK_TOTAL_AT], d_records ? cap : 0);
 }
 
 int dint_state_repair(dint_engine_t *e, const void *d_records, uint64_t n, dint_repair_stats *out, void *stream) {

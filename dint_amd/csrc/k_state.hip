@@ -61,18 +61,6 @@ struct ss_dev_mem {
 };
 
 // ------------------------------------------------------------------------------------------------------ digest
-// the workgroup's digest of the lanes' d, in thread 0 (every thread calls: the wave, one LDS word per wave and number, one barrier)
-__device__ static inline ss_digest ss_block_digest(uint64_t (&red)[SS_TB / 64][3], ss_digest d) {
-  d.rows = sd_wave_sum_u64(d.rows);
-  d.sum = sd_wave_sum_u64(d.sum);
-  d.xr = sd_wave_xor_u64(d.xr);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = d.rows; red[threadIdx.x >> 6][1] = d.sum; red[threadIdx.x >> 6][2] = d.xr; }
-  __syncthreads();
-  ss_digest w = {0, 0, 0};
-  if (threadIdx.x == 0)
-    for (uint32_t k = 0; k < SS_TB / 64; k++) ss_digest_merge(w, ss_digest{red[k][0], red[k][1], red[k][2]});
-  return w;
-}
 // STRIDE = bytes per entry (256: 40-byte values, 128: 8-byte values).  part[4 * workgroup ..] = {rows, sum, xor, 0} of what
 // this workgroup read.
 template <uint32_t STRIDE>
@@ -140,70 +128,7 @@ __global__ void __launch_bounds__(SS_TB) k_state_digest_sum(const unsigned long 
 static_assert(offsetof(kv_hdr, key) == 0 && offsetof(kv_hdr, ver) == 32 && offsetof(kv_hdr, validw) == KV_VALID_OFF, "header layout");
 
 // ------------------------------------------------------------------------------------------------------ diff
-// the rows of one bucket in chain order, read from the table as it lies in HBM.  A position is link << 2 | slot; 0 = the end.
-struct ss_chain {
-  kv_tab t;
-  uint64_t b;
-  __device__ inline bool link_ok(uint32_t link) const { return link == KV_INLINE || (link >= 2u && link - 2u < t.pool_cap); }
-  __device__ inline const uint8_t *entry(uint64_t p) const { return kv_entry_ptr(t, b, (uint32_t)(p >> 2)); }
-  // the first valid slot at or behind (link, slot)
-  __device__ inline uint64_t seek(uint32_t link, uint32_t slot) const {
-    for (uint32_t steps = 0; link_ok(link) && steps < KV_MAX_CHAIN; steps++) {
-      const uint8_t *e = kv_entry_ptr(t, b, link);
-      const uint32_t vw = KV_LD(uint32_t, e + KV_VALID_OFF);
-      for (; slot < 4; slot++)
-        if ((vw >> (8 * slot)) & 0xFFu) return ((uint64_t)link << 2) | slot;
-      link = KV_LD(uint32_t, e + offsetof(kv_hdr, next));
-      slot = 0;
-    }
-    return 0;
-  }
-  __device__ inline uint64_t begin() const { return seek(KV_LD(uint32_t, kv_entry_ptr(t, b, KV_INLINE) + offsetof(kv_hdr, head)), 0); }
-  __device__ inline uint64_t next(uint64_t p) const { return seek((uint32_t)(p >> 2), (uint32_t)(p & 3) + 1); }
-  __device__ inline bool ok(uint64_t p) const { return p != 0; }
-  __device__ inline bool same(uint64_t p, uint64_t q) const { return p == q; }
-  __device__ inline uint64_t key(uint64_t p) const { return KV_LD(uint64_t, entry(p) + 8 * (p & 3)); }
-  __device__ inline uint32_t ver(uint64_t p) const { return KV_LD(uint32_t, entry(p) + 32 + 4 * (p & 3)); }
-  __device__ inline uint32_t val32(uint64_t p, uint32_t w) const {
-    return KV_LD(uint32_t, entry(p) + KV_VAL_OFF + (p & 3) * t.val_size + 4 * w);
-  }
-  __device__ inline uint64_t find(uint64_t k) const {
-    uint32_t link = KV_LD(uint32_t, kv_entry_ptr(t, b, KV_INLINE) + offsetof(kv_hdr, head));
-    for (uint32_t steps = 0; link_ok(link) && steps < KV_MAX_CHAIN; steps++) {
-      kv_hdr h;
-      kv_hdr_load(h, kv_entry_ptr(t, b, link));
-#pragma unroll
-      for (uint32_t i = 0; i < 4; i++)
-        if (kv_valid(h, i) && h.key[i] == k) return ((uint64_t)link << 2) | i;
-      link = h.next;
-    }
-    return 0;
-  }
-};
-#define SS_WALK_BOUND (4u * KV_MAX_CHAIN)  // rows a bucket's walk visits at most: the counts below fit 16 bits each
-
-struct ss_count_emit {
-  uint64_t packed = 0;  // four 16-bit counts, kind k in bits 16k..
-  template <class L, class P>
-  __device__ inline void operator()(uint32_t kind, const L &, P) { packed += 1ull << (16 * kind); }
-};
-template <uint32_t VS>
-struct ss_write_emit {
-  uint8_t *out;
-  uint64_t at, cap;
-  uint32_t table;
-  template <class L, class P>
-  __device__ inline void operator()(uint32_t kind, const L &l, P p) {
-    if (at < cap) {
-      uint32_t w[16];
-      ss_fill_record(w, kind, l, p, table, VS);
-      uint64_t *o = (uint64_t *)(out + at * 64);
-#pragma unroll
-      for (uint32_t k = 0; k < 8; k++) o[k] = (uint64_t)w[2 * k] | ((uint64_t)w[2 * k + 1] << 32);
-    }
-    at++;
-  }
-};
+// (the chain cursor ss_chain, SS_WALK_BOUND and the two emitters are state_dev.h's: k_block.hip walks the same way)
 
 // nothing to say about bucket b without walking a chain?
 template <uint32_t VS>

@@ -1,6 +1,6 @@
-// state_dev.h -- device-side building blocks of the state kernels, the five units that read a server's tables where they lie:
-// k_state.hip (digest / diff / repair), k_image.hip (export / import), k_rehash.hip, k_stats.hip (the table report) and
-// k_verify.hip (the census of chains, lists and pool).  None
+// state_dev.h -- device-side building blocks of the state kernels, the units that read a server's tables where they lie:
+// k_state.hip (digest / diff / repair), k_block.hip (the same block by block), k_image.hip (export / import), k_rehash.hip,
+// k_stats.hip (the table report) and k_verify.hip (the census of chains, lists and pool).  None
 // of it is on a request's path, and no other unit includes it.  wave_excl_scan_u32 is dint_device.h's; the rules that host and
 // device share (the chain walk among them) are state_image.h's.
 #pragma once
@@ -10,6 +10,7 @@
 #include "dint_device.h"
 #include "dint_kv_core.h"
 #include "state_image.h"
+#include "state_sync.h"
 
 #define SD_TB 256u  // threads per workgroup of every kernel that uses the workgroup helpers below
 
@@ -174,3 +175,83 @@ __device__ static inline si_walk sd_bucket_walk(const sd_bucket &ch, F &&on_ovf)
   if (ch.lv.z == KV_INLINE && ch.lv.y == KV_NULL) return si_walk{0, 0, si_valid_count(ch.lv.x), 1, 1};
   return si_walk_chain(ch.lv.z, ch, on_ovf);
 }
+
+// ---- the digest of a workgroup ------------------------------------------------------------------------------------------------
+// the workgroup's digest of the lanes' d, in thread 0 (every thread calls: the wave, one LDS word per wave and number, one barrier)
+__device__ static inline ss_digest ss_block_digest(uint64_t (&red)[SD_TB / 64][3], ss_digest d) {
+  d.rows = sd_wave_sum_u64(d.rows);
+  d.sum = sd_wave_sum_u64(d.sum);
+  d.xr = sd_wave_xor_u64(d.xr);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = d.rows; red[threadIdx.x >> 6][1] = d.sum; red[threadIdx.x >> 6][2] = d.xr; }
+  __syncthreads();
+  ss_digest w = {0, 0, 0};
+  if (threadIdx.x == 0)
+    for (uint32_t k = 0; k < SD_TB / 64; k++) ss_digest_merge(w, ss_digest{red[k][0], red[k][1], red[k][2]});
+  return w;
+}
+
+// ---- a bucket's rows for state_sync.h ss_bucket_diff (k_state.hip the diff, k_block.hip the block rows and the block diff) ----------
+// the rows of one bucket in chain order, read from the table as it lies in HBM.  A position is link << 2 | slot; 0 = the end.
+struct ss_chain {
+  kv_tab t;
+  uint64_t b;
+  __device__ inline bool link_ok(uint32_t link) const { return link == KV_INLINE || (link >= 2u && link - 2u < t.pool_cap); }
+  __device__ inline const uint8_t *entry(uint64_t p) const { return kv_entry_ptr(t, b, (uint32_t)(p >> 2)); }
+  // the first valid slot at or behind (link, slot)
+  __device__ inline uint64_t seek(uint32_t link, uint32_t slot) const {
+    for (uint32_t steps = 0; link_ok(link) && steps < KV_MAX_CHAIN; steps++) {
+      const uint8_t *e = kv_entry_ptr(t, b, link);
+      const uint32_t vw = KV_LD(uint32_t, e + KV_VALID_OFF);
+      for (; slot < 4; slot++)
+        if ((vw >> (8 * slot)) & 0xFFu) return ((uint64_t)link << 2) | slot;
+      link = KV_LD(uint32_t, e + offsetof(kv_hdr, next));
+      slot = 0;
+    }
+    return 0;
+  }
+  __device__ inline uint64_t begin() const { return seek(KV_LD(uint32_t, kv_entry_ptr(t, b, KV_INLINE) + offsetof(kv_hdr, head)), 0); }
+  __device__ inline uint64_t next(uint64_t p) const { return seek((uint32_t)(p >> 2), (uint32_t)(p & 3) + 1); }
+  __device__ inline bool ok(uint64_t p) const { return p != 0; }
+  __device__ inline bool same(uint64_t p, uint64_t q) const { return p == q; }
+  __device__ inline uint64_t key(uint64_t p) const { return KV_LD(uint64_t, entry(p) + 8 * (p & 3)); }
+  __device__ inline uint32_t ver(uint64_t p) const { return KV_LD(uint32_t, entry(p) + 32 + 4 * (p & 3)); }
+  __device__ inline uint32_t val32(uint64_t p, uint32_t w) const {
+    return KV_LD(uint32_t, entry(p) + KV_VAL_OFF + (p & 3) * t.val_size + 4 * w);
+  }
+  __device__ inline uint64_t find(uint64_t k) const {
+    uint32_t link = KV_LD(uint32_t, kv_entry_ptr(t, b, KV_INLINE) + offsetof(kv_hdr, head));
+    for (uint32_t steps = 0; link_ok(link) && steps < KV_MAX_CHAIN; steps++) {
+      kv_hdr h;
+      kv_hdr_load(h, kv_entry_ptr(t, b, link));
+#pragma unroll
+      for (uint32_t i = 0; i < 4; i++)
+        if (kv_valid(h, i) && h.key[i] == k) return ((uint64_t)link << 2) | i;
+      link = h.next;
+    }
+    return 0;
+  }
+};
+#define SS_WALK_BOUND (4u * KV_MAX_CHAIN)  // rows a bucket's walk visits at most: the counts below fit 16 bits each
+
+struct ss_count_emit {
+  uint64_t packed = 0;  // four 16-bit counts, kind k in bits 16k..
+  template <class L, class P>
+  __device__ inline void operator()(uint32_t kind, const L &, P) { packed += 1ull << (16 * kind); }
+};
+template <uint32_t VS>
+struct ss_write_emit {
+  uint8_t *out;
+  uint64_t at, cap;
+  uint32_t table;
+  template <class L, class P>
+  __device__ inline void operator()(uint32_t kind, const L &l, P p) {
+    if (at < cap) {
+      uint32_t w[16];
+      ss_fill_record(w, kind, l, p, table, VS);
+      uint64_t *o = (uint64_t *)(out + at * 64);
+#pragma unroll
+      for (uint32_t k = 0; k < 8; k++) o[k] = (uint64_t)w[2 * k] | ((uint64_t)w[2 * k + 1] << 32);
+    }
+    at++;
+  }
+};

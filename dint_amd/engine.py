@@ -73,6 +73,7 @@ class Engine:
         _lib.check(self._L.dint_engine_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self.shard_index, self.shard_count = shard_index, max(1, shard_count)
+        self.device_index = device
         self.flags = flags
         self.val_size = 8 if self.workload == Workload.SMALLBANK else 40
         self.pass_max = int(self._L.dint_max_pass(self._h))
@@ -250,6 +251,57 @@ class Engine:
         self.last_repair = {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
         _lib.check(rc)
         return self.last_repair
+
+    # ---- block sync (dint_state_block_digest / _select / _rows / _diff) ------------------------------------
+    def state_block_digest(self, block_buckets: int, d_out=None, stream: int = 0):
+        """dint_state_block_digest: {rows, sum, xr, 0} (32 bytes) per block of `block_buckets` consecutive local buckets -- a
+        power of two, 64 .. 2^20 -- of every table, in block-id order (table 0's blocks, then table 1's ...; csrc/state_block.h),
+        into the HBM buffer d_out (a torch tensor of 32 bytes per block; None allocates one of int64 [blocks, 4] on this
+        engine's device).  Returns (tensor, blocks, stats); stats["blocks"] = the blocks per table.  A sharded engine is taken."""
+        import torch
+
+        s = _lib.BlockStats()
+        if d_out is None:
+            n = _lib.check(self._L.dint_state_block_digest(self._h, block_buckets, None, 0, C.byref(s), stream))  # (counts only)
+            d_out = torch.empty((max(n, 1), 4), dtype=torch.int64, device=self._torch_device())
+        n = _lib.check(self._L.dint_state_block_digest(self._h, block_buckets, _ptr(d_out), d_out.numel() * d_out.element_size() // 32, C.byref(s), stream))
+        return d_out, n, s.as_dict()
+
+    def state_block_select(self, d_a, d_b, n_blocks: int, d_ids=None, cap=None, stream: int = 0):
+        """dint_state_block_select: the ascending ids (int32 tensor, on d_a's device) of the blocks whose 32 bytes differ between
+        the two digest arrays.  Returns (ids tensor, how many differ in all); the first `cap` (default: all) are written."""
+        import torch
+
+        cap = n_blocks if cap is None else cap
+        if d_ids is None:
+            d_ids = torch.empty(max(cap, 1), dtype=torch.int32, device=d_a.device)
+        n = _lib.check(self._L.dint_state_block_select(_ptr(d_a), _ptr(d_b), n_blocks, _ptr(d_ids), cap, stream))
+        return d_ids, n
+
+    def state_block_rows(self, block_buckets: int, d_ids, n_ids: int, d_records=None, cap: int = 0, stream: int = 0):
+        """dint_state_block_rows: the visible rows of the listed blocks (d_ids: int32 tensor in HBM, strictly ascending) as 64-byte
+        records in the HBM buffer d_records (room for cap; None with cap = 0 only counts): ascending id, ascending bucket, chain
+        order.  Returns (records written, total the blocks hold)."""
+        s = _lib.BlockStats()
+        n = _lib.check(self._L.dint_state_block_rows(self._h, block_buckets, _ptr(d_ids) if n_ids else None, n_ids,
+                                                     None if d_records is None else _ptr(d_records), cap, C.byref(s), stream))
+        return n, int(s.total)
+
+    def state_block_diff(self, block_buckets: int, d_ids, n_ids: int, d_rows, n_rows: int, d_records=None, cap: int = 0, stream: int = 0):
+        """dint_state_block_diff: what must be done to THIS engine inside the listed blocks to make its visible rows those of the
+        row list d_rows (state_block_rows' records of the other side, carried to this engine's device), in state_diff's record
+        form, order and stats; the output goes to state_repair unchanged.  Returns (records written, stats).  A list that is
+        out of order, names a table the workload has not or holds a row of an unlisted block raises DintError (DINT_EINVAL) with
+        nothing written."""
+        s = _lib.DiffStats()
+        n = _lib.check(self._L.dint_state_block_diff(self._h, block_buckets, _ptr(d_ids) if n_ids else None, n_ids, _ptr(d_rows) if n_rows else None,
+                                                     n_rows, None if d_records is None else _ptr(d_records), cap, C.byref(s), stream))
+        return n, {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+
+    def _torch_device(self):
+        import torch
+
+        return torch.device("cuda", self.device_index) if getattr(self, "device_index", -1) >= 0 else torch.device("cuda")
 
     # ---- state image (dint_state_export / dint_state_import) ---------------------------------------------
     def state_export(self, dst_index: int = 0, dst_count: int = 1, d_buf=None, stream: int = 0):

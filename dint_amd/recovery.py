@@ -16,6 +16,8 @@ once per row and emits the batch on the GPU); primary and replica are engines on
 A replica that fell behind (the primary's ring lapped the shipper) cannot be caught up from the log.  `resync` compares the
 two engines' tables where they lie (dint_state_diff) and writes the difference into the replica WITH the primary's versions
 (dint_state_repair; csrc/k_state.hip); `Engine.state_digest` says in 64 bytes per table whether two engines hold the same rows.
+`resync_blocks` is the same for a replica on another device: digests per block of buckets, and only the rows of the blocks that
+differ are carried (dint_state_block_digest / _select / _rows / _diff; csrc/k_block.hip).
 
 Moving a server to another shard layout is neither: `reshard` carries the tables of a complete set of engines (1 or G
 shards) into a blank set of H shards as state images (dint_state_export / dint_state_import; csrc/k_image.hip) -- entry for
@@ -155,6 +157,62 @@ def resync(primary, replica, cap: int = 1 << 20, max_rounds: int = 8, buf=None) 
         records += replica.state_repair(buf, n)["applied"]
         rounds += 1
     return {"rounds": rounds, "records": records, "digests_equal": digests_equal(primary, replica)}
+
+
+def resync_blocks(primary, replica, block_buckets: int = 4096, cap: int = 1 << 20, max_rounds: int = 8, carry=None) -> dict:
+    """`resync` for a replica on ANOTHER device: the two sides compare digests of blocks of `block_buckets` buckets
+    (Engine.state_block_digest; csrc/state_block.h) and only the rows of the blocks that differ travel.  A round: block digests on
+    both sides; the primary's carried over; select on the replica; the differing ids carried back; their visible rows on the
+    primary (state_block_rows); the rows carried over; state_block_diff then state_repair on the replica.  `carry(tensor)` moves
+    a tensor from one engine's device to the other's -- default: `.to()` the other engine's device; everything else stays where
+    it is.  Rounds repeat as `resync`'s do: a deleted visible duplicate uncovers the next, and `cap` (records per buffer, one
+    on each side) may be shorter than the rows or the diff -- then a round takes the leading blocks whose rows fit, so one block's
+    rows must fit `cap`.  Returns {rounds, records, blocks_differing (in the first round), digest_bytes, id_bytes, row_bytes
+    (what was carried), digests_equal (Engine.state_digest, the strict check)}.  Equal replicas cost the two digest calls and one
+    select and carry the digests only.  Both engines: one workload, n_rows and flags, unsharded (state_repair routes no rows),
+    quiet for the duration."""
+    import torch
+
+    to_replica = carry if carry is not None else (lambda t: t.to(replica._torch_device()))
+    to_primary = carry if carry is not None else (lambda t: t.to(primary._torch_device()))
+    out = {"rounds": 0, "records": 0, "blocks_differing": 0, "digest_bytes": 0, "id_bytes": 0, "row_bytes": 0}
+    rows_buf = rec_buf = None
+    while True:
+        da, nb, _ = primary.state_block_digest(block_buckets)
+        db, nb_r, _ = replica.state_block_digest(block_buckets)
+        if nb != nb_r:
+            raise DintError(f"resync_blocks: {nb} blocks on the primary, {nb_r} on the replica: not engines of one size and shard")
+        da_r = to_replica(da[:nb])
+        out["digest_bytes"] += 32 * nb
+        ids, nd = replica.state_block_select(da_r, db, nb)
+        if out["rounds"] == 0:
+            out["blocks_differing"] = nd
+        if nd == 0 or out["rounds"] >= max_rounds:
+            break
+        ids_p = to_primary(ids[:nd])
+        out["id_bytes"] += 4 * nd
+        take = nd
+        while True:  # the leading blocks whose rows fit the buffer
+            _, total = primary.state_block_rows(block_buckets, ids_p, take)
+            if total <= cap:
+                break
+            if take == 1:
+                raise DintError(f"resync_blocks: block {int(ids[0])} holds {total} rows, the buffers {cap}: a larger cap or smaller blocks")
+            take //= 2
+        if rows_buf is None:
+            rows_buf = torch.empty(cap * LOG_REC.itemsize, dtype=torch.uint8, device=primary._torch_device())
+            rec_buf = torch.empty(cap * LOG_REC.itemsize, dtype=torch.uint8, device=replica._torch_device())
+        n, _ = primary.state_block_rows(block_buckets, ids_p, take, rows_buf, cap)
+        rows_r = to_replica(rows_buf[:n * LOG_REC.itemsize])
+        out["row_bytes"] += n * LOG_REC.itemsize
+        m, st = replica.state_block_diff(block_buckets, ids, take, rows_r, n, rec_buf, cap)
+        if m:
+            out["records"] += replica.state_repair(rec_buf, m)["applied"]
+        out["rounds"] += 1
+        if st["total"] == 0 and take == nd:
+            break  # (the blocks differ in what the diff does not see: shadowed duplicates; digests_equal says so)
+    out["digests_equal"] = digests_equal(primary, replica)
+    return out
 
 
 def image_pieces(G: int, H: int) -> list:
@@ -480,14 +538,18 @@ class LogShipper:
         self.lost += lost
         return out
 
-    def resync(self) -> dict:
+    def resync(self, blocks=None) -> dict:
         """Replica := primary, from the tables.  First the primary's drain cursor moves to the tail (a drain whose records
         are dropped): the records still in the ring are in the primary's rows already, and replayed on top of the repaired
-        replica they would bump versions twice.  Both engines quiet for the duration."""
+        replica they would bump versions twice.  Both engines quiet for the duration.  blocks=B: through `resync_blocks` with
+        blocks of B buckets (a replica on another device); None: `resync`."""
         while True:
             n, _ = self.primary.log_drain_device(self.buf, self.cap)
             if n == 0:
                 break
-        out = resync(self.primary, self.replica, cap=self.cap, buf=self.buf)
+        if blocks is None:
+            out = resync(self.primary, self.replica, cap=self.cap, buf=self.buf)
+        else:
+            out = resync_blocks(self.primary, self.replica, block_buckets=blocks, cap=self.cap)
         self.resyncs += 1
         return out

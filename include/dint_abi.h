@@ -387,6 +387,62 @@ typedef struct dint_repair_stats {
  * the call returns DINT_ENOMEM (as dint_wait).  Same refusals as dint_state_diff for the one engine. */
 int dint_state_repair(dint_engine_t *b, const void *d_records, uint64_t n, dint_repair_stats *out, void *stream);
 
+/* ---- block sync (v5, additive): two replicas on DIFFERENT devices compared block by block, only the blocks that differ shipped ----
+ * dint_state_diff wants both engines on one device; between two GPUs dint_state_digest says "not equal" and nothing about where,
+ * and an image carries everything.  These four calls are the steps in between; what crosses between the devices -- digests one way,
+ * block ids back, rows forth -- is plain bytes in device memory that the CALLER moves.
+ *
+ * A BLOCK is block_buckets consecutive LOCAL buckets of one table (dint_amd/csrc/state_block.h is the rule): block_buckets a power
+ * of two, 64 .. 2^20, anything else DINT_EINVAL; a table's last block may be short.  Block ids are u32 and run over the tables in
+ * table order: table 0's blocks, then table 1's ...  Two engines of the same workload, n_rows, shard_index / shard_count,
+ * DINT_FLAG_LOCK_SAME_KEY and block_buckets have the same blocks, and that is what the caller must pair.  A sharded engine is
+ * accepted: it is compared with the same shard of the other set.
+ *
+ * The contract is the state sync's: synchronous, ordered behind the engine's pending work on `stream` (NULL = the engine's own);
+ * store / tatp / smallbank engines only (lock / log engines: DINT_ESTATE); an announced batch pending: DINT_ESTATE; no engine is
+ * modified; nothing of a caller's buffer is trusted.  Device buffers are 8-byte aligned (ids: 4).  Scratch is allocated in the
+ * engine on first use, grown to what a call needs and kept.  One host synchronisation per call, two for block_rows / block_diff
+ * when there is something to write (the total is read first, as dint_state_diff does). */
+typedef struct dint_block_digest {
+  uint64_t rows, sum, xr; /* as dint_table_digest, over the valid slots of the chains of the block's buckets */
+  uint64_t reserved;      /* 0 */
+} dint_block_digest;
+typedef struct dint_block_stats {
+  uint64_t total;         /* block_digest: the blocks; block_rows: the records the listed blocks hold (also when cap is smaller) */
+  uint32_t n_blocks;      /* blocks of the engine at this block_buckets */
+  uint32_t n_tables;
+  uint32_t blocks[5];     /* blocks per table: table t's ids are [blocks[0] + .. + blocks[t - 1], ... + blocks[t]) */
+  uint32_t block_buckets;
+  uint64_t reserved[3];
+} dint_block_stats;
+/* (v5, additive) d_out[id] (DEVICE memory, room for cap_blocks digests) = the digest of block id, for every block; returns the number
+ * of blocks (cap_blocks smaller: DINT_EINVAL, nothing written).  d_out == NULL only counts.  Digested is every valid slot reached by
+ * walking the chains of the block's buckets (bounded by 4096 entries, links checked), shadowed duplicates included: on tables that
+ * dint_state_verify finds sound, the blocks of a table merge (rows and sum add, xr xors) to dint_state_digest's entry. */
+int64_t dint_state_block_digest(dint_engine_t *e, uint64_t block_buckets, void *d_out, uint64_t cap_blocks, dint_block_stats *out_stats,
+                                void *stream);
+/* (v5, additive) needs no engine: d_a, d_b = two arrays of n_blocks digests on one device; d_ids (u32, room for cap) takes the
+ * ascending ids of the blocks whose 32 bytes differ.  Returns how many there are in all; the first cap are written.  Synchronises
+ * `stream` (NULL: the null stream) once; one word of scratch is allocated and freed by the call. */
+int64_t dint_state_block_select(const void *d_a, const void *d_b, uint32_t n_blocks, void *d_ids, uint64_t cap, void *stream);
+/* (v5, additive) the VISIBLE rows (per key the first valid slot in chain order, as in dint_state_diff) of the n_ids blocks listed in
+ * d_ids (DEVICE memory, u32, strictly ascending) as canonical 64-byte records {key, val zero-padded to 40, ver, is_del = 0, table}
+ * into d_records.  Order: ascending id, ascending bucket, chain order.  Returns the records written (the first cap of that order);
+ * out_stats->total how many there are.  d_records == NULL with cap == 0 only counts.  Ids not strictly ascending or out of
+ * range: DINT_EINVAL, nothing written. */
+int64_t dint_state_block_rows(dint_engine_t *e, uint64_t block_buckets, const void *d_ids, uint32_t n_ids, void *d_records, uint64_t cap,
+                              dint_block_stats *out_stats, void *stream);
+/* (v5, additive) what must be done to b INSIDE the listed blocks to make its visible rows those of the row list d_rows (n_rows
+ * records of dint_state_block_rows' form and order, DEVICE memory on b's device), in dint_state_diff's record form, order and
+ * stats: ascending table and bucket; the list's rows of a bucket in list order, then b's rows that the list lacks in b's chain
+ * order.  The output goes to dint_state_repair unchanged.  A check reads the whole list before anything is written: every row's
+ * table is in range and it is no delete record, every row is home (fasthash64 % hash size, shard included) to a bucket of a
+ * listed block, (table, bucket) is non-decreasing, no bucket has more than 16,384 rows; ids as for block_rows.  A list or id
+ * list that fails: DINT_EINVAL with not a byte written.  A key that appears twice in one bucket's run: the first is the visible
+ * one.  n_rows >= 2^32 - 16: DINT_EINVAL. */
+int64_t dint_state_block_diff(dint_engine_t *b, uint64_t block_buckets, const void *d_ids, uint32_t n_ids, const void *d_rows, uint64_t n_rows,
+                              void *d_records, uint64_t cap, dint_diff_stats *out_stats, void *stream);
+
 /* ---- state image (v5, additive): an engine's tables moved to another shard layout, cloned or checkpointed -- on the device ----
  * An IMAGE holds everything of one source engine that belongs to one destination shard, entry for entry: kv workloads -- the
  * inline entries (whole stride: keys, versions, valid bytes, values, tatp lock bytes, smallbank counters, owner keys) and every

@@ -285,6 +285,20 @@ int dint_state_compact_view_host(const dint_tables_view *view, struct dint_table
 int dint_state_compact_view(int32_t device, const dint_tables_view *view, struct dint_table_compact *out, uint32_t cap_tables,
                             uint32_t flags, void *stream);
 
+/* ---- block sync: the rule over caller-provided memory (dint_amd/csrc/state_block.h) ------------------------------------------
+ * dint_state_block_digest / dint_state_block_rows / dint_state_block_diff (include/dint_abi.h) over tables the CALLER describes in
+ * HOST memory, with the view and its check of the verify forms above (a view that fails it: DINT_EINVAL).  Digests, ids, rows and
+ * records are host memory (rows and records at any alignment); arguments, order, refusals and return values are the device calls'.  A refused call
+ * writes not a byte.  No device call. */
+struct dint_block_digest; /* include/dint_abi.h */
+struct dint_block_stats;
+int64_t dint_state_block_digest_host(const dint_tables_view *view, uint64_t block_buckets, struct dint_block_digest *out, uint64_t cap_blocks,
+                                     struct dint_block_stats *out_stats);
+int64_t dint_state_block_rows_host(const dint_tables_view *view, uint64_t block_buckets, const uint32_t *ids, uint32_t n_ids, void *records,
+                                   uint64_t cap, struct dint_block_stats *out_stats);
+int64_t dint_state_block_diff_host(const dint_tables_view *view, uint64_t block_buckets, const uint32_t *ids, uint32_t n_ids, const void *rows,
+                                   uint64_t n_rows, void *records, uint64_t cap, struct dint_diff_stats *out_stats);
+
 #ifdef __cplusplus
 }
 #endif

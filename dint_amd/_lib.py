@@ -14,6 +14,12 @@ LIB_PATH = os.environ.get("DINT_LIB_PATH") or os.path.join(HERE, "libdint.so")  
 ABI_VERSION = 5
 #: dint_config.flags (include/dint_abi.h)
 FLAG_KV_ROUNDS, FLAG_COPY_STREAMS, FLAG_LOCK_SAME_KEY, FLAG_KV_NO_HOT, FLAG_INPUTS_READY = 1, 2, 4, 8, 16
+#: a shard of a replica set: takes routed records in state_repair / state_diff / log_apply_device / log_apply_folded
+FLAG_SHARD_REPLICA = 32
+#: records per workgroup of dint_records_route's kernels (csrc/state_route.h RR_TILE; dint_records_route_tile() says the same)
+ROUTE_TILE = 512
+#: shards dint_records_route takes at most
+ROUTE_MAX_SHARDS = 255
 MICRO_BATCH = 65536
 
 #: every symbol include/dint_abi.h declares (checked by tests/test_abi.py)
@@ -30,6 +36,7 @@ SYMBOLS = [
     "dint_state_export", "dint_state_import", "dint_state_rehash", "dint_state_stats",
     "dint_state_verify", "dint_state_compact",
     "dint_state_block_digest", "dint_state_block_select", "dint_state_block_rows", "dint_state_block_diff",
+    "dint_records_route",
 ]
 #: dint_log_apply_folded_device flags
 FOLD_DRY_RUN = 1
@@ -265,6 +272,7 @@ def load() -> C.CDLL:
         "dint_state_block_select": (i64, [vp, vp, u32, vp, u64, vp]),
         "dint_state_block_rows": (i64, [vp, u64, vp, u32, vp, u64, C.POINTER(BlockStats), vp]),
         "dint_state_block_diff": (i64, [vp, u64, vp, u32, vp, u64, vp, u64, C.POINTER(DiffStats), vp]),
+        "dint_records_route": (i64, [vp, u32, vp, u64, vp, u64, vp, vp]),
         "dint_state_export": (C.c_int, [vp, u32, u32, vp, u64, C.POINTER(ImageStats), vp]),
         "dint_state_import": (C.c_int, [vp, vp, u64, C.POINTER(ImageStats), vp]),
         "dint_state_rehash": (C.c_int, [vp, C.POINTER(vp), u32, u32, C.POINTER(RehashStats), vp]),
@@ -292,6 +300,9 @@ def load() -> C.CDLL:
         "dint_state_block_digest_host": (i64, [C.POINTER(TablesView), u64, vp, u64, C.POINTER(BlockStats)]),
         "dint_state_block_rows_host": (i64, [C.POINTER(TablesView), u64, vp, u32, vp, u64, C.POINTER(BlockStats)]),
         "dint_state_block_diff_host": (i64, [C.POINTER(TablesView), u64, vp, u32, vp, u64, vp, u64, C.POINTER(DiffStats)]),
+        # ... and the record routing's rule (csrc/state_route.h) over a list in host memory
+        "dint_records_route_host": (i64, [u32, u64, u32, vp, u64, vp, vp]),
+        "dint_records_route_tile": (u32, []),
         # ... and the rehash's layout rule (csrc/state_rehash.h) over keys in source order
         "dint_state_rehash_place_host": (i64, [vp, u64, u64, u32, u32, vp, vp, vp]),
     }

@@ -8,6 +8,7 @@
 #include "dint_kv_core.h"
 #include "state_block.h"
 #include "state_image.h"
+#include "state_route.h"
 
 #define DINT_KV_MAX_TABLES 5
 #define DINT_KV_CTL_BYTES (64 + 24 * KV_NLISTS)  // per table: pool_top, free_head[], pend_head[2][] (two sets: dint_kv_core.h, kv_pool_rotate)
@@ -76,6 +77,33 @@ static inline uint32_t dint_kv_cap_mult() {
   const unsigned long m = v && *v ? strtoul(v, nullptr, 10) : 64ul;
   return (uint32_t)(m < 2 ? 2 : m > 256 ? 256 : m);
 }
+// the global bucket counts of a kv workload's tables for dint_config.n_rows (0 = the reference's size), as dint_kv_create builds
+// them and dint_records_route_host routes by them; returns the number of tables (store / tatp / smallbank: 1 / 5 / 2)
+static inline uint32_t dint_kv_hash_sizes(uint32_t workload, uint64_t n_rows, uint64_t hs[DINT_KV_MAX_TABLES], uint32_t *val_size) {
+  uint32_t n_tables;
+  for (uint32_t t = 0; t < DINT_KV_MAX_TABLES; t++) hs[t] = 0;
+  if (workload == DINT_WL_STORE) {
+    const uint64_t n = n_rows ? n_rows : 2000000ull;  // store/udp/tatp.h:10
+    n_tables = 1;
+    *val_size = 40;
+    hs[0] = n * 18 / 4;  // store/udp/server.cc:112-114: 12 rows per subscriber * 3/2 / 4 slots
+  } else if (workload == DINT_WL_TATP) {
+    const uint64_t n = n_rows ? n_rows : 7000000ull;  // tatp/udp/tatp.h:28
+    n_tables = 5;
+    *val_size = 40;
+    hs[0] = hs[1] = n * 3 / 2 / 4;   // tatp/udp/server_shard.cc:75-76
+    hs[2] = hs[3] = n * 15 / 4 / 4;  // :77-78
+    hs[4] = n * 45 / 8 / 4;          // :79
+  } else {
+    const uint64_t n = n_rows ? n_rows : 24000000ull;  // smallbank/udp/smallbank.h:17
+    n_tables = 2;
+    *val_size = 8;
+    hs[0] = hs[1] = n * 3 / 2 / 4;  // smallbank/udp/server_shard.cc:75-76
+  }
+  for (uint32_t t = 0; t < n_tables; t++)
+    if (hs[t] == 0) hs[t] = 1;
+  return n_tables;
+}
 int dint_kv_create(dint_kv *kv, uint32_t workload, uint64_t n_rows, dint_shard shard, uint32_t pool_entries = 0,
                    uint32_t flags = 0);
 void dint_kv_destroy(dint_kv *kv);
@@ -125,7 +153,7 @@ dint_kv_fmt dint_kv_format(uint32_t workload);
 // ---- state sync (k_state.hip; state_sync.h): digest / diff / repair of the tables' rows ---------------------------
 struct dint_state_scratch {
   unsigned long long *words;  // [32] device words: [0..3] the diff's records by kind (state_sync.h SS_*), [4] their number,
-                              // [8] the repair's "records out of order" flag, [9..12] {updated, inserted, deleted, refused},
+                              // [8] the repair's "records out of order" flag, [9..12] {updated, inserted, deleted, refused}, [14] the home check's flag,
                               // [16 ..] the digest: {rows, sum, xor, 0} per table
   uint32_t *blk_cnt;          // [nb] the diff's records per workgroup of 256 buckets, all tables in table order
   uint64_t *blk_off;          // [nb] ... their exclusive scan
@@ -144,6 +172,9 @@ void dint_launch_state_diff_count(const dint_kv &a, const dint_kv &b, dint_state
 void dint_launch_state_diff_write(const dint_kv &a, const dint_kv &b, dint_state_scratch s, void *d_records, uint64_t cap, hipStream_t st);
 // s.words[8] != 0 afterwards: the n records are not grouped by (table, bucket) in ascending order, or name a table that is not there
 void dint_launch_state_repair_check(const dint_kv &kv, const void *d_records, uint64_t n, dint_state_scratch s, hipStream_t st);
+// s.words[DINT_STATE_HOME_AT] != 0 afterwards: one of the n records (in any order) names a table that is not there or is home to another shard
+#define DINT_STATE_HOME_AT 14u
+void dint_launch_state_home_check(const dint_kv &kv, const void *d_records, uint64_t n, dint_state_scratch s, hipStream_t st);
 // applies the records; emptied overflow entries go to pend set `pend_set` (dint_kv_core.h kv_pool_rotate); counts into s.words[9..12]
 void dint_launch_state_repair(const dint_kv &kv, const void *d_records, uint64_t n, uint32_t pend_set, dint_dev_stats *stats,
                               dint_state_scratch s, hipStream_t st);
@@ -245,6 +276,20 @@ void dint_launch_block_diff_count(const dint_kv &kv, const bk_geom &g, const voi
                                   dint_block_scratch s, hipStream_t st);
 void dint_launch_block_diff_write(const dint_kv &kv, const bk_geom &g, const void *d_ids, uint32_t n_ids, uint64_t lanes, const void *d_rows, uint32_t n_rows,
                                   dint_block_scratch s, void *d_records, uint64_t cap, hipStream_t st);
+
+// ---- record routing (k_rroute.hip; state_route.h): a record list partitioned, stably, by home shard of another layout -----------
+struct dint_rroute_scratch {
+  unsigned long long *words = nullptr;  // [DINT_RROUTE_WORDS] device words: [0] the first record without a home (RR_NO_INDEX: none), [1] the
+                                        // scan's total, [2 + h] offsets[h] for h = 0 .. H
+  uint32_t *cnt = nullptr;              // [cnt_n] records per (shard, tile), shard-major ...
+  uint64_t *off = nullptr;              // ... their exclusive scan: the first output record of every (shard, tile)
+  uint64_t cnt_n = 0;
+};
+#define DINT_RROUTE_WORDS (2u + RR_MAX_SHARDS + 1u)
+// n > 0, rr_tiles(n) * g.n_shards <= RR_MAX_COUNTS and <= s.cnt_n.  The check's finding and the offsets into s.words ...
+void dint_launch_rroute_count(const rr_geom &g, const void *d_rec, uint64_t n, dint_rroute_scratch s, hipStream_t st);
+// ... then (same stream, the host has seen a good list that fits) the n records into d_out
+void dint_launch_rroute_write(const rr_geom &g, const void *d_rec, uint64_t n, dint_rroute_scratch s, void *d_out, hipStream_t st);
 
 // ---- state image (k_image.hip; state_image.h): the tables written out for another shard layout and read back --------
 struct dint_image_scratch {

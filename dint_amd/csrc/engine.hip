@@ -142,6 +142,9 @@ struct dint_engine {
   // block sync (dint_state_block_digest / _rows / _diff): result words, the digest's partials, the id list's and the lanes' arrays;
   // allocated on first use, grown to what a call needs and kept
   dint_block_scratch block{};
+  // record routing (dint_records_route): the result words and the (shard, tile) counts with their scan; allocated on first use, grown
+  // to what a call needs and kept
+  dint_rroute_scratch rroute{};
   // table report (dint_state_stats): the workgroups' partial reports and the tables' reports, allocated on the first call
   dint_stats_scratch tstats{};
   // table verify (dint_state_verify): the owner words, partial reports and reclaim arrays, allocated on the first call and kept
@@ -681,11 +684,50 @@ int block_reserve(dint_engine *e, uint64_t chunks, uint64_t ids, uint64_t lanes,
     if (int rc = grow((void **)&s.run_lo, sizeof(uint32_t), (void **)&s.run_hi, sizeof(uint32_t), s.run_n, lanes)) return rc;
   return 0;
 }
+int state_launched();
+// record routing scratch: grows to what a call needs and is kept (no zero fill: every call writes what it reads)
+void rroute_free(dint_engine *e) {
+  dint_rroute_scratch &s = e->rroute;
+  hipFree(s.words); hipFree(s.cnt); hipFree(s.off);
+  s = dint_rroute_scratch{};
+}
+int rroute_reserve(dint_engine *e, uint64_t counts) {
+  dint_rroute_scratch &s = e->rroute;
+  if (!s.words)
+    if (int rc = dev_alloc((void **)&s.words, DINT_RROUTE_WORDS * sizeof(unsigned long long), false)) return rc;
+  if (counts <= s.cnt_n) return 0;
+  hipFree(s.cnt); hipFree(s.off);
+  s.cnt = nullptr; s.off = nullptr; s.cnt_n = 0;
+  int rc = dev_alloc((void **)&s.cnt, (size_t)counts * sizeof(uint32_t), false);
+  if (!rc) rc = dev_alloc((void **)&s.off, (size_t)counts * sizeof(uint64_t), false);
+  if (rc) {
+    hipFree(s.cnt); hipFree(s.off);
+    s.cnt = nullptr; s.off = nullptr;
+    return rc;
+  }
+  s.cnt_n = counts;
+  return 0;
+}
+// a shard of a replica set (DINT_FLAG_SHARD_REPLICA): it places records at their local bucket and refuses foreign ones
+bool shard_replica(const dint_engine *e) { return e->shard.count > 1 && (e->cfg.flags & DINT_FLAG_SHARD_REPLICA) != 0; }
 // the checks the three state calls share for one engine, before any GPU work
 int state_check(const dint_engine *e, bool sharded_ok) {
   if (!e->kv.n_tables) return fail(DINT_ESTATE, "workload has no kv table");
-  if (!sharded_ok && e->shard.count > 1) return fail(DINT_EINVAL, "a sharded engine: rows are not routed here");
+  if (!sharded_ok && e->shard.count > 1 && !shard_replica(e)) return fail(DINT_EINVAL, "a sharded engine: rows are not routed here");
   return 0;
+}
+// a flagged shard before a log replay: all n records are read once, and a record of another shard or of no table refuses the list
+// (on the engine's stream, already ordered; one synchronisation)
+int shard_home_check(dint_engine *e, const void *d_records, uint64_t n, hipStream_t st) {
+  if (int rc = state_alloc(e, false)) return rc;
+  dint_launch_state_home_check(e->kv, d_records, n, e->state, st);
+  if (int rc = state_launched()) return rc;
+  unsigned long long bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, e->state.words + DINT_STATE_HOME_AT, sizeof bad, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return bad ? fail(DINT_EINVAL, "a record is home to another shard or names a table the workload has not (dint_records_route makes a "
+                                 "shard's piece); nothing was applied")
+             : 0;
 }
 // ... under the engine's mutex: the state calls read the tables where they lie, so none runs between an announcement and its pass
 int state_quiet(dint_engine *e) {
@@ -1028,6 +1070,7 @@ void dint_engine_destroy(dint_engine_t *e) {
   fold_free(e);
   state_free(e);
   block_free(e);
+  rroute_free(e);
   hipFree(e->tstats.part); hipFree(e->tstats.out);
   e->tstats = dint_stats_scratch{};
   dint_verify_free(e->tverify);
@@ -1632,7 +1675,7 @@ int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, u
   if (!e || (n && !d_records)) return fail(DINT_EINVAL, "null argument");
   const uint32_t wl = e->cfg.workload;
   if (wl != DINT_WL_TATP && wl != DINT_WL_SMALLBANK) return fail(DINT_ESTATE, "workload has no table a log replays into");
-  if (e->shard.count > 1) return fail(DINT_EINVAL, "a sharded engine: the log would have to be routed first");
+  if (e->shard.count > 1 && !shard_replica(e)) return fail(DINT_EINVAL, "a sharded engine: the log would have to be routed first");
   std::lock_guard<std::mutex> lk(e->mu);
   if (int rc = ahead_settle(e)) return rc;
   if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
@@ -1644,6 +1687,8 @@ int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, u
   const dint_replay_scratch &r = e->replay;
   hipStream_t st = e->stream;
   if (int rc = order_stream(e, st)) return rc;
+  if (shard_replica(e))
+    if (int rc = shard_home_check(e, d_records, n, st)) return rc;
   HIP_TRY(hipMemsetAsync(r.counts, 0, 4 * sizeof(unsigned long long), st));
   const bool timed = e->timer.on && out;  // stage times: the stream is drained chunk by chunk (a diagnostic)
   if (timed)
@@ -1674,7 +1719,7 @@ int dint_log_apply_folded_device(dint_engine_t *e, const void *d_records, uint64
   if ((uintptr_t)d_records & 15) return fail(DINT_EINVAL, "records: 16-byte aligned");
   const uint32_t wl = e->cfg.workload;
   if (wl != DINT_WL_TATP && wl != DINT_WL_SMALLBANK) return fail(DINT_ESTATE, "workload has no table a log replays into");
-  if (e->shard.count > 1) return fail(DINT_EINVAL, "a sharded engine: the log would have to be routed first");
+  if (e->shard.count > 1 && !shard_replica(e)) return fail(DINT_EINVAL, "a sharded engine: the log would have to be routed first");
   std::lock_guard<std::mutex> lk(e->mu);
   if (int rc = ahead_settle(e)) return rc;
   if (e->ahead.valid) return fail(DINT_ESTATE, "a batch announced by dint_submit_device_ahead is pending");
@@ -1692,6 +1737,8 @@ int dint_log_apply_folded_device(dint_engine_t *e, const void *d_records, uint64
   const dint_fold_scratch &f = e->fold;
   hipStream_t st = e->stream;
   if (int rc = order_stream(e, st)) return rc;
+  if (shard_replica(e))
+    if (int rc = shard_home_check(e, d_records, n, st)) return rc;
   HIP_TRY(hipMemsetAsync(f.counts, 0, DINT_FOLD_COUNTS * sizeof(unsigned long long), st));
   if (!dry) HIP_TRY(hipMemsetAsync(e->replay.counts, 0, 4 * sizeof(unsigned long long), st));
   const bool timed = e->timer.on && out;
@@ -1887,6 +1934,8 @@ int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uin
     if (a->kv.hash_size[t] != b->kv.hash_size[t]) return fail(DINT_EINVAL, "the engines differ in n_rows");
   if (int rc = state_check(a, false)) return rc;
   if (int rc = state_check(b, false)) return rc;
+  if (a->shard.count != b->shard.count || (a->shard.count > 1 && a->shard.index != b->shard.index))
+    return fail(DINT_EINVAL, "the engines differ in shard layout: a shard is compared with the same shard of another set");
   std::unique_lock<std::mutex> l0(*std::min(&a->mu, &b->mu)), l1(*std::max(&a->mu, &b->mu));  // address order
   if (int rc = state_quiet(a)) return rc;
   if (int rc = state_quiet(b)) return rc;
@@ -1912,6 +1961,50 @@ int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uin
     out->total = h[4]; out->only_a = h[0]; out->only_b = h[1]; out->val_differs = h[2]; out->ver_only = h[3];
   }
   return (int64_t)std::min<uint64_t>(h[4], d_records ? cap : 0);
+}
+
+// ---- record routing (k_rroute.hip; state_route.h) -------------------------------------------------------------------------------
+int64_t dint_records_route(dint_engine_t *e, uint32_t dst_count, const void *d_records, uint64_t n, void *d_out, uint64_t cap, uint64_t *offsets,
+                           void *stream) {
+  if (!e || !offsets) return fail(DINT_EINVAL, "null argument");
+  if (dst_count == 0 || dst_count > RR_MAX_SHARDS) return fail(DINT_EINVAL, "dst_count %u: 1 .. %u shards", dst_count, RR_MAX_SHARDS);
+  if (n && (!d_records || !d_out)) return fail(DINT_EINVAL, "n records need an input and an output buffer");
+  if (((uintptr_t)d_records & 15) || ((uintptr_t)d_out & 15)) return fail(DINT_EINVAL, "records and output: 16-byte aligned");
+  if (!e->kv.n_tables) return fail(DINT_ESTATE, "workload has no kv table");
+  if (n > (1ull << 57)) return fail(DINT_EINVAL, "too many records");
+  const uint8_t *src = (const uint8_t *)d_records, *dst = (const uint8_t *)d_out;
+  if (n && src < dst + n * 64 && dst < src + n * 64) return fail(DINT_EINVAL, "the input and the output overlap");
+  if (rr_tiles(n) * dst_count > RR_MAX_COUNTS) return fail(DINT_EINVAL, "%llu records to %u shards: more (shard, tile) pairs than one scan takes", (unsigned long long)n, dst_count);
+  if (cap < n) return fail(DINT_ENOMEM, "%llu records, room for %llu", (unsigned long long)n, (unsigned long long)cap);
+  if (n == 0) {
+    for (uint32_t h = 0; h <= dst_count; h++) offsets[h] = 0;
+    return 0;
+  }
+  std::lock_guard<std::mutex> lk(e->mu);  // (the scratch is the engine's; its tables are not touched: no quiet engine is asked for)
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = rroute_reserve(e, rr_tiles(n) * dst_count)) return rc;
+  rr_geom g;
+  g.n_tables = e->kv.n_tables;
+  g.n_shards = dst_count;
+  for (uint32_t t = 0; t < RR_MAX_TABLES; t++) g.mod[t] = t < e->kv.n_tables ? e->kv.h.mod[t] : dint_make_mod(1);
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  dint_launch_rroute_count(g, d_records, n, e->rroute, st);
+  if (int rc = state_launched()) return rc;
+  unsigned long long h[DINT_RROUTE_WORDS];
+  HIP_TRY(hipMemcpyAsync(h, e->rroute.words, (size_t)(dst_count + 3) * sizeof h[0], hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the one synchronisation of the call)
+  const bool good = h[0] == RR_NO_INDEX && h[2 + dst_count] == n;
+  if (good) {
+    dint_launch_rroute_write(g, d_records, n, e->rroute, d_out, st);
+    if (int rc = state_launched()) return rc;
+  }
+  if (int rc = mark_stream(e, st)) return rc;
+  if (h[0] != RR_NO_INDEX)
+    return fail(DINT_EINVAL, "record %llu has no home: its table byte names a table the workload has not; nothing was written", h[0]);
+  if (!good) return fail(DINT_EHIP, "record routing: the counts do not add up to the list (an internal error); nothing was written");
+  for (uint32_t k = 0; k <= dst_count; k++) offsets[k] = h[2 + k];
+  return (int64_t)n;
 }
 
 // ---- block sync (k_block.hip; state_block.h) ----------------------------------------------------------------------------------

@@ -61,7 +61,10 @@ k_fold_keys(const uint4 *__restrict__ rec, uint32_t m, const kv_dev *__restrict_
   const uint64_t key = fd_key(v0);
   row[i] = lr_row((uint8_t)table, key);
   idx[i] = i;
-  place[i] = table < kv->n_tables ? lf_place(table, dint_fastmod(dint_hash_key(key), kv->mod[table])) : lf_place(LF_BAD_TABLE, 0);
+  // (the LOCAL bucket: k_fold_probe indexes this engine's own table, and the repair records leave in the shard's order.  A record of
+  // another shard never gets here -- the call's check pass refused the list -- and would be set aside like one of a bad table)
+  const uint64_t b = table < kv->n_tables ? rr_local(key, table, kv->mod, kv->shard_index, kv->shard_count) : SR_FOREIGN;
+  place[i] = b != SR_FOREIGN ? lf_place(table, b) : lf_place(LF_BAD_TABLE, 0);
 }
 
 __global__ void __launch_bounds__(FD_TB)
@@ -118,7 +121,7 @@ k_fold_probe(const kv_dev *__restrict__ kv, const uint64_t *__restrict__ place_s
     occ = 2;  // (a table the workload has not: the serial replay answers such a record)
   } else {
     const kv_tab t = kv->tab[table];
-    const uint64_t b = lf_place_bucket(place);  // (< hash_size = n_local of an unsharded engine: dint_fastmod)
+    const uint64_t b = lf_place_bucket(place);  // (< n_local: the local bucket k_fold_keys placed it at)
     const sd_bucket ch = sd_bucket_at(t, b);
     const bool ok = si_chain_walk(ch.head(), ch, [&](uint32_t, uint32_t link, uint32_t validw) {
       if (!validw) return true;
@@ -377,7 +380,7 @@ extern "C" int64_t dint_log_fold_host(uint32_t workload, uint32_t n_tables, cons
     std::vector<uint64_t> place(n);
     std::vector<uint32_t> idx(n);
     for (uint64_t i = 0; i < n; i++)
-      place[i] = rec[i].table < n_tables ? lf_place(rec[i].table, dint_fastmod(dint_hash_key(rec[i].key), mod[rec[i].table]))
+      place[i] = rec[i].table < n_tables ? lf_place(rec[i].table, rr_local(rec[i].key, rec[i].table, mod.data(), 0, 1))  // (the host form: unsharded)
                                          : lf_place(LF_BAD_TABLE, 0);
     std::iota(idx.begin(), idx.end(), 0u);
     std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) {

@@ -270,24 +270,7 @@ int dint_kv_create(dint_kv *kv, uint32_t workload, uint64_t n_rows, dint_shard s
   kv->workload = workload;
   kv->h.same_key = (workload == DINT_WL_TATP && (flags & DINT_FLAG_LOCK_SAME_KEY)) ? 1 : 0;
   uint64_t hs[DINT_KV_MAX_TABLES] = {0, 0, 0, 0, 0};
-  if (workload == DINT_WL_STORE) {
-    const uint64_t n = n_rows ? n_rows : 2000000ull;  // store/udp/tatp.h:10
-    kv->n_tables = 1;
-    kv->val_size = 40;
-    hs[0] = n * 18 / 4;  // store/udp/server.cc:112-114: 12 rows per subscriber * 3/2 / 4 slots
-  } else if (workload == DINT_WL_TATP) {
-    const uint64_t n = n_rows ? n_rows : 7000000ull;  // tatp/udp/tatp.h:28
-    kv->n_tables = 5;
-    kv->val_size = 40;
-    hs[0] = hs[1] = n * 3 / 2 / 4;   // tatp/udp/server_shard.cc:75-76
-    hs[2] = hs[3] = n * 15 / 4 / 4;  // :77-78
-    hs[4] = n * 45 / 8 / 4;          // :79
-  } else {
-    const uint64_t n = n_rows ? n_rows : 24000000ull;  // smallbank/udp/smallbank.h:17
-    kv->n_tables = 2;
-    kv->val_size = 8;
-    hs[0] = hs[1] = n * 3 / 2 / 4;  // smallbank/udp/server_shard.cc:75-76
-  }
+  kv->n_tables = dint_kv_hash_sizes(workload, n_rows, hs, &kv->val_size);
   const uint32_t stride = kv->val_size == 40 ? 256u : 128u;
   const uint32_t count = shard.count ? shard.count : 1;
   kv->h.n_tables = kv->n_tables;

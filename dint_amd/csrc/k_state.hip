@@ -200,8 +200,18 @@ __device__ static inline uint64_t ss_rec_key(const uint8_t *r) { return *(const 
 __device__ static inline bool ss_rec_place(const kv_dev *kv, const uint8_t *r, uint64_t *place) {
   const uint32_t table = r[offsetof(LrRecord, table)];
   if (table >= kv->n_tables) return false;
-  *place = ((uint64_t)table << 56) | dint_fastmod(dint_hash_key(ss_rec_key(r)), kv->mod[table]);
+  // (the LOCAL bucket: the global one on an unsharded engine; a record that is home to another shard has no place here)
+  const uint64_t b = rr_local(ss_rec_key(r), table, kv->mod, kv->shard_index, kv->shard_count);
+  if (b == SR_FOREIGN) return false;
+  *place = ((uint64_t)table << 56) | b;
   return true;
+}
+// bad |= 1: a record that names a table the workload has not or is home to another shard (a log for dint_log_apply_device: any order)
+__global__ void __launch_bounds__(SS_TB) k_state_home_check(const uint8_t *__restrict__ rec, uint64_t n, const kv_dev *__restrict__ kv,
+                                                            uint32_t *bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * SS_TB + threadIdx.x;
+  uint64_t me;
+  if (i < n && !ss_rec_place(kv, rec + i * 64, &me)) atomicOr(bad, 1u);
 }
 __global__ void __launch_bounds__(SS_TB) k_state_repair_check(const uint8_t *__restrict__ rec, uint64_t n, const kv_dev *__restrict__ kv,
                                                               uint32_t *bad) {
@@ -315,6 +325,13 @@ void dint_launch_state_repair_check(const dint_kv &kv, const void *d_records, ui
   if (n == 0) return;
   hipLaunchKernelGGL(k_state_repair_check, dim3((uint32_t)((n + SS_TB - 1) / SS_TB)), dim3(SS_TB), 0, st, (const uint8_t *)d_records, n,
                      (const kv_dev *)kv.d_dev, (uint32_t *)(s.words + 8));
+}
+
+void dint_launch_state_home_check(const dint_kv &kv, const void *d_records, uint64_t n, dint_state_scratch s, hipStream_t st) {
+  (void)hipMemsetAsync(s.words + DINT_STATE_HOME_AT, 0, sizeof(unsigned long long), st);
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_state_home_check, dim3((uint32_t)((n + SS_TB - 1) / SS_TB)), dim3(SS_TB), 0, st, (const uint8_t *)d_records, n,
+                     (const kv_dev *)kv.d_dev, (uint32_t *)(s.words + DINT_STATE_HOME_AT));
 }
 
 void dint_launch_state_repair(const dint_kv &kv, const void *d_records, uint64_t n, uint32_t pend_set, dint_dev_stats *stats,

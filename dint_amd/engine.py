@@ -298,6 +298,30 @@ class Engine:
                                                      n_rows, None if d_records is None else _ptr(d_records), cap, C.byref(s), stream))
         return n, {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
 
+    # ---- record routing (dint_records_route) ------------------------------------------------------------------
+    def records_route(self, dst_count: int, d_records, n: int, d_out=None, stream: int = 0, wait: bool = True):
+        """dint_records_route: the n 64-byte records at d_records (HBM: a torch uint8 tensor or a device pointer, 16-byte aligned)
+        partitioned, stably, by their home among `dst_count` shards -- (fasthash64(key) % the table's bucket count) % dst_count,
+        csrc/state_route.h -- into d_out (None allocates a uint8 tensor of n records on this engine's device).  Returns (d_out,
+        offsets): shard h's records are d_out[64 * offsets[h] : 64 * offsets[h + 1]], in their input order.  This engine only
+        lends its workload and n_rows (and its stream and scratch): its shard layout is ignored and its tables are not touched.
+        A record whose table the workload has not raises DintError (DINT_EINVAL) with nothing written.  The call returns with
+        the offsets known and the records' write enqueued on `stream` (0 = this engine's own); wait=True then waits for it, so that
+        any other engine or stream may read d_out; wait=False leaves that to the caller (stream_signal, or work on `stream`)."""
+        import torch
+
+        if d_out is None:
+            d_out = torch.empty(max(n, 1) * 64, dtype=torch.uint8, device=self._torch_device())
+        cap = d_out.numel() * d_out.element_size() // 64 if hasattr(d_out, "numel") else n
+        off = (C.c_uint64 * (dst_count + 1))()
+        _lib.check(self._L.dint_records_route(self._h, dst_count, _ptr(d_records) if n else None, n, _ptr(d_out), cap, off, stream))
+        if wait and n:
+            if stream:
+                torch.cuda.synchronize(self._torch_device())
+            else:
+                self.sync()
+        return d_out, list(off)
+
     def _torch_device(self):
         import torch
 

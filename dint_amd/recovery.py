@@ -144,7 +144,8 @@ def resync(primary, replica, cap: int = 1 << 20, max_rounds: int = 8, buf=None) 
     {rounds: repair calls made, records: records applied, digests_equal}.  What the diff cannot see is not repaired -- a
     shadowed duplicate of a key that stays visible, on either side -- and digests_equal, the strict check, then says False
     (as it does when max_rounds did not suffice).  The caller keeps both engines quiet for the
-    duration; both must be unsharded engines of one workload and size on one device."""
+    duration; both must be engines of one workload and size on one device: unsharded, or the SAME shard of two sets, every sharded
+    one created with FLAG_SHARD_REPLICA (the diff is then in that shard's local bucket order, which its repair takes)."""
     import torch
 
     if buf is None:
@@ -169,8 +170,9 @@ def resync_blocks(primary, replica, block_buckets: int = 4096, cap: int = 1 << 2
     on each side) may be shorter than the rows or the diff -- then a round takes the leading blocks whose rows fit, so one block's
     rows must fit `cap`.  Returns {rounds, records, blocks_differing (in the first round), digest_bytes, id_bytes, row_bytes
     (what was carried), digests_equal (Engine.state_digest, the strict check)}.  Equal replicas cost the two digest calls and one
-    select and carry the digests only.  Both engines: one workload, n_rows and flags, unsharded (state_repair routes no rows),
-    quiet for the duration."""
+    select and carry the digests only.  Both engines: one workload, n_rows and flags, quiet for the duration; unsharded, or
+    the same shard of two sets with the replica created with FLAG_SHARD_REPLICA (the block calls take any shard; the repair that
+    applies their result takes a flagged one)."""
     import torch
 
     to_replica = carry if carry is not None else (lambda t: t.to(replica._torch_device()))
@@ -213,6 +215,38 @@ def resync_blocks(primary, replica, block_buckets: int = 4096, cap: int = 1 << 2
             break  # (the blocks differ in what the diff does not see: shadowed duplicates; digests_equal says so)
     out["digests_equal"] = digests_equal(primary, replica)
     return out
+
+
+def route_records(geom, d_records, n: int, dst_count: int, d_out=None, stream: int = 0) -> list:
+    """Engine.records_route as views: the n records at d_records (a torch uint8 tensor in HBM) routed to a layout of `dst_count`
+    shards; returns [(tensor view of shard h's records, their number) for h in range(dst_count)] -- pieces of ONE buffer, each in
+    the input's order.  `geom` = any engine of the workload and n_rows on that device (its own shard layout does not matter)."""
+    out, off = geom.records_route(dst_count, d_records, n, d_out, stream)
+    return [(out[64 * off[h]:64 * off[h + 1]], off[h + 1] - off[h]) for h in range(dst_count)]
+
+
+def _layout(engines) -> int:
+    engines = list(engines)
+    G = len(engines)
+    if not all(e.shard_count == G and e.shard_index == i for i, e in enumerate(engines)):
+        raise DintError("a shard set is a complete layout in index order: shard i of G at position i")
+    return G
+
+
+def resync_set(primaries, replicas, blocks=None, carry=None, cap: int = 1 << 20) -> dict:
+    """`resync` (blocks=None) or `resync_blocks` (blocks=B buckets per block; `carry` as there) pair by pair for two shard sets of
+    ONE layout: replica shard i := primary shard i.  The replicas carry FLAG_SHARD_REPLICA, and for blocks=None so do the
+    primaries (state_diff compares flagged shards only; the block calls take any shard).  One engine on each side: plain `resync`.  Returns {"shards": the per-pair results, "records": their sum, "digests_equal": digest_sum of the two sets is
+    equal}.  Sets of different layouts are refused: moving tables between layouts is `reshard`'s job (state images), not a
+    resync's."""
+    primaries, replicas = list(primaries), list(replicas)
+    G, H = _layout(primaries), _layout(replicas)
+    if G != H:
+        raise DintError(f"resync_set: {G} primary shards, {H} replica shards: a resync pairs equal layouts; recovery.reshard moves "
+                        "tables to another layout")
+    per = [resync(p, r, cap=cap) if blocks is None else resync_blocks(p, r, block_buckets=blocks, cap=cap, carry=carry)
+           for p, r in zip(primaries, replicas)]
+    return {"shards": per, "records": sum(x["records"] for x in per), "digests_equal": digest_sum(primaries) == digest_sum(replicas)}
 
 
 def image_pieces(G: int, H: int) -> list:
@@ -366,7 +400,7 @@ def verify_tables(engines, reclaim: bool = False) -> dict:
 
 
 def hash_sizes(workload, n_rows: int) -> list:
-    """the global bucket count of every table of an engine created with n_rows: dint_kv_create's formulas (csrc/k_kv.hip),
+    """the global bucket count of every table of an engine created with n_rows: dint_kv_create's formulas (csrc/dint_kv.h dint_kv_hash_sizes),
     mirrored -- what Engine.hash_size(t) returns.  n_rows = 0 is the reference's own size."""
     wl = Workload(workload)
     if wl == Workload.STORE:
@@ -553,3 +587,69 @@ class LogShipper:
             out = resync_blocks(self.primary, self.replica, block_buckets=blocks, cap=self.cap)
         self.resyncs += 1
         return out
+
+
+class ShardSetShipper:
+    """`LogShipper.step()` for shard SETS: follows the logs of a primary set of G shards into a replica set of H shards (created
+    with FLAG_SHARD_REPLICA when H > 1).  A step drains every primary shard's ring on its device, routes the drain to the
+    replicas' layout (Engine.records_route; skipped when the layouts are equal: shard i's log is then replica i's piece as it
+    stands -- `routes` counts the route calls made), carries piece (i -> j) to replica j's device (`carry(tensor, engine)`;
+    default `.to()` its device) and applies the pieces of destination j one after the other, folded or not.
+
+    Per-row order holds under ANY order of the pieces: a key lives in exactly one source shard, so all records of a row are in
+    one source's log, the route is stable, and pieces of different sources touch disjoint rows.
+
+    `lost` is reported per source as LogShipper reports it; what a ring overwrote cannot be replayed.  `resync()` brings the
+    replicas back from the primaries' tables through `resync_set` when the layouts are equal, and raises DintError when they
+    are not (a resync pairs equal layouts; `reshard` moves tables between layouts)."""
+
+    def __init__(self, primaries, replicas, cap: int = 1 << 20, chunk: int = 0, fold: bool = False, carry=None):
+        import torch
+
+        self.primaries, self.replicas = list(primaries), list(replicas)
+        self.G, self.H = _layout(self.primaries), _layout(self.replicas)
+        assert all(e.workload == self.primaries[0].workload for e in self.primaries + self.replicas)
+        self.cap, self.chunk, self.fold = cap, chunk, fold
+        self.carry = carry if carry is not None else (lambda t, e: t.to(e._torch_device()))
+        self.bufs = [torch.empty(cap * LOG_REC.itemsize, dtype=torch.uint8, device=p._torch_device()) for p in self.primaries]
+        self.outs = [torch.empty(cap * LOG_REC.itemsize, dtype=torch.uint8, device=p._torch_device()) for p in self.primaries] if self.G != self.H else []
+        self.shipped = self.routes = self.resyncs = 0
+        self.lost = [0] * self.G
+
+    def step(self) -> dict:
+        """one drain of every source and the replay of its pieces.  Returns {applied, commits / inserts / deletes (tatp) or acks
+        (smallbank), folded / deferred (fold), lost: [per source], pieces: [(i, j, records)]}"""
+        apply = apply_log_folded if self.fold else apply_log_device
+        tot, pieces, lost = {}, [], []
+        for i, p in enumerate(self.primaries):
+            n, lo = p.log_drain_device(self.bufs[i], self.cap)
+            lost.append(lo)
+            self.lost[i] += lo
+            self.shipped += n
+            if n == 0:
+                continue
+            if self.G == self.H:
+                parts = [(i, self.bufs[i][:n * LOG_REC.itemsize], n)]
+            else:
+                self.routes += 1
+                parts = [(j, v, m) for j, (v, m) in enumerate(route_records(p, self.bufs[i], n, self.H, self.outs[i])) if m]
+            for j, view, m in parts:
+                r = self.replicas[j]
+                st = apply(r, self.carry(view, r), m, self.chunk)
+                pieces.append((i, j, m))
+                for k, v in st.items():
+                    tot[k] = tot.get(k, 0) + v
+        tot.setdefault("applied", 0)
+        tot["lost"], tot["pieces"] = lost, pieces
+        return tot
+
+    def resync(self, blocks=None) -> dict:
+        """replicas := primaries, from the tables (see LogShipper.resync): every primary's drain cursor moves to its tail first."""
+        if self.G != self.H:
+            raise DintError(f"ShardSetShipper.resync: {self.G} primary shards, {self.H} replica shards: a resync pairs equal layouts; "
+                            "recovery.reshard moves tables to another layout")
+        for i, p in enumerate(self.primaries):
+            while p.log_drain_device(self.bufs[i], self.cap)[0]:
+                pass
+        self.resyncs += 1
+        return resync_set(self.primaries, self.replicas, blocks=blocks, cap=self.cap)

@@ -73,6 +73,14 @@ extern "C" {
                                       more sets of pass scratch, ~0.5 GB of address space each (touched as filled).  The kv
                                       workloads' form of the promise is per call: dint_submit_device_ahead */
 
+#define DINT_FLAG_SHARD_REPLICA 0x20u /* (= 32) store / tatp / smallbank engines with shard_count > 1: the engine is one shard of a REPLICA
+                                         set and takes what writes to a replica -- dint_state_repair, dint_state_diff (against the
+                                         same shard of another set), dint_log_apply_device and dint_log_apply_folded_device -- over
+                                         records that dint_records_route brought to its layout: a record is placed at its LOCAL
+                                         bucket, and a list that holds a record of another shard is refused whole.  Without the flag
+                                         a sharded engine refuses these calls, as it always has; an unsharded engine ignores it.
+                                         The request path, the block sync and every other call are the same either way */
+
 /* workloads (dint_config.workload) */
 enum {
   DINT_WL_FASST = 0,     /* lock_fasst: 9-byte {u8 type; u32 lid; u32 ver}            net.h:23-29 */
@@ -291,9 +299,12 @@ typedef struct dint_apply_stats {
  * own stream, which must already be ordered behind whatever produced the records (dint_log_drain_device returns with them
  * complete; dint_stream_wait otherwise).  Returns when the work is queued unless out != NULL, which synchronises the stream
  * and fills the counts.  The records stay untouched.  Refused before any GPU work: a workload without a KV log target
- * (DINT_ESTATE), a sharded engine (DINT_EINVAL: routing a log is not done here), a batch announced by
+ * (DINT_ESTATE), a sharded engine without DINT_FLAG_SHARD_REPLICA (DINT_EINVAL: the log must be routed first), a batch announced by
  * dint_submit_device_ahead still pending (DINT_ESTATE, as dint_snapshot).  The replica's own log is not appended to (backup
- * operations never are).  Scratch of ~200 bytes per record of a chunk is allocated on the first call and kept. */
+ * operations never are).  Scratch of ~200 bytes per record of a chunk is allocated on the first call and kept.
+ * A sharded engine created with DINT_FLAG_SHARD_REPLICA takes the piece dint_records_route made for it: one check pass reads all n
+ * records before the first chunk, and a record that is home to another shard or names a table the workload has not gives DINT_EINVAL
+ * with nothing applied (its READ probe would go unanswered and be misread as "row absent"); this costs one synchronisation. */
 int dint_log_apply_device(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t chunk, dint_apply_stats *out);
 
 #define DINT_FOLD_DRY_RUN 1u
@@ -316,8 +327,9 @@ typedef struct dint_fold_stats {
  * pool use may differ ("state is rows only", below).  A bucket in which a row the chunk touches is held twice or more is DEFERRED:
  * all its records of the chunk go through dint_log_apply_device's own chunk routine in log order (folded and deferred buckets are
  * disjoint, so the two write paths commute).
- * Contract, refusals and stream ordering are dint_log_apply_device's: lock / log / store engines DINT_ESTATE, a sharded engine
- * DINT_EINVAL, an announced batch pending DINT_ESTATE, d_records == NULL with n > 0 DINT_EINVAL, n == 0 returns 0; flags other than
+ * Contract, refusals and stream ordering are dint_log_apply_device's (DINT_FLAG_SHARD_REPLICA included: the fold places a row at its
+ * local bucket, the whole list is checked before the first chunk, also for a dry run): lock / log / store engines DINT_ESTATE, a sharded engine
+ * without that flag DINT_EINVAL, an announced batch pending DINT_ESTATE, d_records == NULL with n > 0 DINT_EINVAL, n == 0 returns 0; flags other than
  * DINT_FOLD_DRY_RUN and records not 16-byte aligned: DINT_EINVAL.  Keys stay below 2^60, as for the serial replay.  The records
  * stay untouched; the replica's lock words, log ring and log cursor are left alone.  FOLDED records are not counted in the
  * replica's request counters (dint_stats batches / requests; nor in missing_keys, which the serial replay bumps for a smallbank
@@ -366,7 +378,9 @@ typedef struct dint_diff_stats {
  * strict check).  The order is fixed: ascending table, ascending bucket; inside a bucket a's rows in a's chain order, then the
  * b-only rows in b's.  Returns the number of records written (<= cap; the first cap of that order); out (may be NULL) says how
  * many there are.  d_records == NULL with cap == 0 only counts.  Neither engine is modified.  Refused before any GPU work:
- * a == b, a null engine, engines of different workloads, table sizes or devices, a sharded engine on either side (DINT_EINVAL);
+ * a == b, a null engine, engines of different workloads, table sizes or devices, a sharded engine on either side (DINT_EINVAL)
+ * -- unless both engines are the SAME shard (shard_index and shard_count equal) and every sharded one was created with
+ * DINT_FLAG_SHARD_REPLICA: then the order is ascending table, ascending LOCAL bucket, what that shard's dint_state_repair takes;
  * lock / log engines, an announced batch pending on either (DINT_ESTATE).  Scratch of 12 bytes per 256 buckets is allocated in
  * a on the first call and kept. */
 int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uint64_t cap, dint_diff_stats *out, void *stream);
@@ -384,8 +398,29 @@ typedef struct dint_repair_stats {
  * records of one bucket are applied in order by one lane; buckets run in parallel.  Records out of order, or naming a table the
  * workload has not: DINT_EINVAL with the tables untouched.  b's lock words, log ring, log cursor and request counters are left
  * alone.  An insert that finds the pool full is not done: `refused` and dint_stats.pool_exhausted count it, the rest is applied,
- * the call returns DINT_ENOMEM (as dint_wait).  Same refusals as dint_state_diff for the one engine. */
+ * the call returns DINT_ENOMEM (as dint_wait).  Same refusals as dint_state_diff for the one engine.  A sharded engine created with
+ * DINT_FLAG_SHARD_REPLICA is taken: "bucket" is then the shard's local bucket (global bucket / shard_count), and a record that is
+ * home to another shard is refused like a record out of order -- DINT_EINVAL, tables untouched.  A list in the unsharded order that
+ * went through dint_records_route arrives in this order. */
 int dint_state_repair(dint_engine_t *b, const void *d_records, uint64_t n, dint_repair_stats *out, void *stream);
+
+/* (v5, additive) ROUTE: the n canonical 64-byte records at d_records (DEVICE memory) partitioned, stably, by their home among
+ * dst_count shards -- home = (fasthash64(key) % the table's bucket count) % dst_count, dint_amd/csrc/state_route.h -- into d_out (DEVICE
+ * memory on the same device, room for cap records): shard 0's records in their input order, then shard 1's ...; offsets (HOST, dst_count
+ * + 1 entries) says where: shard h's records are d_out[offsets[h] .. offsets[h + 1]), offsets[dst_count] = n.  Returns n.  What it
+ * is for: a list produced under one layout -- a drained log, a dint_state_diff or dint_state_block_rows list of an unsharded primary or
+ * of one shard of G -- becomes the lists of the shards of another; log order per row and the repair's bucket order both survive it.
+ * `geom` is any store / tatp / smallbank engine on the device that holds the records (lock / log engines: DINT_ESTATE): only its
+ * workload and n_rows, which fix the bucket counts, are used; its own shard layout is ignored, its tables are neither read nor
+ * written, and it need not be quiet.  The call orders itself behind the engine's pending work on `stream` (NULL = the engine's own)
+ * and synchronises it ONCE, to read the check's result and the offsets; the records are written behind that, in stream order.
+ * dst_count == 1 is a copy.  d_records == NULL with n == 0: returns 0, every offset 0.  Refused before a byte of d_out is written:
+ * dst_count 0 or above 255, a buffer that is not 16-byte aligned, input and output ranges that overlap, more than 2^32 - 16
+ * (shard, 512-record tile) pairs (DINT_EINVAL); cap < n (DINT_ENOMEM); a record whose table the workload has not -- it has no home --
+ * (DINT_EINVAL; dint_last_error names the first such index).  Two calls on the same input write the same bytes.  Scratch of 12 bytes
+ * per (shard, tile) is allocated in geom on first use, grown to what a call needs and kept. */
+int64_t dint_records_route(dint_engine_t *geom, uint32_t dst_count, const void *d_records, uint64_t n, void *d_out, uint64_t cap,
+                           uint64_t *offsets, void *stream);
 
 /* ---- block sync (v5, additive): two replicas on DIFFERENT devices compared block by block, only the blocks that differ shipped ----
  * dint_state_diff wants both engines on one device; between two GPUs dint_state_digest says "not equal" and nothing about where,

@@ -299,6 +299,17 @@ int64_t dint_state_block_rows_host(const dint_tables_view *view, uint64_t block_
 int64_t dint_state_block_diff_host(const dint_tables_view *view, uint64_t block_buckets, const uint32_t *ids, uint32_t n_ids, const void *rows,
                                    uint64_t n_rows, void *records, uint64_t cap, struct dint_diff_stats *out_stats);
 
+/* ---- record routing: the rule over caller-provided memory (dint_amd/csrc/state_route.h) ----------------------------------------
+ * dint_records_route (include/dint_abi.h) over a list in HOST memory, at any alignment: the stable partition of the n 64-byte records
+ * at rec by home shard -- (fasthash64(key) % the table's bucket count) % dst_count, the bucket counts those of an engine of
+ * `workload` (store / tatp / smallbank; anything else DINT_ESTATE) created with n_rows -- into out (room for n records), and the
+ * dst_count + 1 offsets.  Returns n.  dst_count 0 or above 255, a missing buffer, input and output overlapping, a record whose table
+ * the workload has not (dint_last_error names the first): DINT_EINVAL, with neither out nor offsets written.  No device call. */
+int64_t dint_records_route_host(uint32_t workload, uint64_t n_rows, uint32_t dst_count, const void *rec, uint64_t n, void *out,
+                                uint64_t *offsets);
+/* records per workgroup of dint_records_route's kernels: the sizes at which the device path changes shape (one tile, two, ...) */
+uint32_t dint_records_route_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

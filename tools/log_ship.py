@@ -2,7 +2,7 @@
 """Replay one primary's log into two fresh replicas -- once over the host (dint_log_drain + recovery.apply_log), once
 without leaving the GPU (dint_log_drain_device + dint_log_apply_device) -- and say what each costs.
 
-    tools/log_ship.py [--workload tatp|smallbank] [--rows N] [--records M] [--chunk C] [--timeout S] [--fold]
+    tools/log_ship.py [--workload tatp|smallbank] [--rows N] [--records M] [--chunk C] [--timeout S] [--fold] [--shards G:H]
 
 A primary takes M committed writes (the log record, then the primary operation, as tests/test_ebpf_surface.py
 _committed_writes sends them; rows drawn Zipf-0.8: updates, and for tatp one delete in four and inserts of rows that are
@@ -18,6 +18,15 @@ deferred_records, and whether the digests of the two paths' end states are equal
 recorded on torch's current stream, not the engine's own: a figure is the time between two synchronised points around the call
 (queueing, the kernels, the per-chunk wait), not device time on the stream that did the work; the stage times are the engine's own
 events on its stream.
+
+--shards G:H measures the step between two shard SETS on the one device: a primary set of G shards (G = 1: one unsharded engine)
+takes the writes, each shard its home requests; every shard's log is drained and routed to a replica set of H shards
+(dint_records_route; replicas created with DINT_FLAG_SHARD_REPLICA), and the pieces are applied destination by destination.
+Printed: the route's time over all G drains -- median and range of 7 runs between HIP events on the stream the route runs on, after
+a warm run; the figure includes the call's one host synchronisation -- beside a plain device-to-device copy of the same bytes
+measured the same way in the same process, their ratio, the per-shard apply times unfolded and folded (wall clock around the
+synchronous calls, one run after a warm one, the replicas put back by restore), and whether the replica set's digests add up to
+the primary set's after each.
 
 All GPU work happens in ONE child process under a time limit; the parent never opens the GPU."""
 import argparse
@@ -75,8 +84,9 @@ def writes(rng, rows, live, n, tatp):
     return m
 
 
-def primary_with_log(a):
-    """a primary that has taken a.records committed writes and been snapshotted: (prim, fresh, same, tatp)"""
+def primary_with_log(a, G=1):
+    """a primary that has taken a.records committed writes and been snapshotted: (prim, fresh, same, tatp).  G > 1: a primary SET of
+    G shards, each of which took its home requests in order; `prim` is then the list."""
     import numpy as np
 
     from dint_amd import wire
@@ -102,6 +112,13 @@ def primary_with_log(a):
     rng = np.random.default_rng(1)
     prim = fresh()
     tk = [prim.dump_rows(t)[0] for t in range(tables)]
+    prims = [prim]
+    if G > 1:
+        import torch
+
+        prims = [Engine(wl, n_rows=a.rows, log_entries=max(a.records, 1024), shard_index=i, shard_count=G) for i in range(G)]
+        for e in prims:
+            e.populate(a.rows)
     if tatp:  # + rows that do not exist yet, as _committed_writes
         new = [k[:max(1, len(k) // 20)] + np.uint64(1 << 44) for k in tk]
         new = [x[~np.isin(x, k)] for x, k in zip(new, tk)]
@@ -115,11 +132,22 @@ def primary_with_log(a):
     left = a.records
     while left:
         n = min(left, prim.pass_max // 2)
-        prim.submit(writes(rng, rows, live, n, tatp))
+        m = writes(rng, rows, live, n, tatp)
+        if G == 1:
+            prim.submit(m)
+        else:  # the home of every request from the engines' own rule (dint_home_shard), then every shard its part
+            d_m = torch.from_numpy(np.frombuffer(m.tobytes(), np.uint8).copy()).cuda()
+            d_home = torch.empty(len(m), dtype=torch.uint8, device="cuda")
+            prims[0].home_shard(d_m, len(m), d_home)
+            prims[0].sync()
+            home = d_home.cpu().numpy()
+            for i, e in enumerate(prims):
+                e.submit(m[home == i])
         left -= n
-    assert prim.stats()["missing_keys"] == 0, "the generator sent a write to a row that is not there"
-    prim.snapshot()
-    return prim, fresh, same, tatp
+    for e in prims:
+        assert e.stats()["missing_keys"] == 0, "the generator sent a write to a row that is not there"
+        e.snapshot()
+    return (prim if G == 1 else prims), fresh, same, tatp
 
 
 def child_fold(a):
@@ -162,6 +190,89 @@ def child_fold(a):
     out["digests_equal"] = digest["folded"] == digest["unfolded"]
     print(json.dumps(out))
     return 0 if out["counts_equal"] and out["digests_equal"] else 1
+
+
+def child_shards(a):
+    import statistics
+
+    import torch
+
+    from dint_amd import _lib, recovery, wire
+    from dint_amd.engine import Engine
+
+    G, H = a.shards
+    prims, _, _, tatp = primary_with_log(a, G)
+    prims = prims if G > 1 else [prims]
+    wl = wire.Workload.TATP if tatp else wire.Workload.SMALLBANK
+    bufs, ns = [], []
+    for p in prims:
+        buf = torch.empty(a.records * 64, dtype=torch.uint8, device="cuda")
+        n, lost = p.log_drain_device(buf, a.records)
+        assert lost == 0
+        bufs.append(buf)
+        ns.append(n)
+    assert sum(ns) == a.records
+    outs = [torch.empty(max(n, 1) * 64, dtype=torch.uint8, device="cuda") for n in ns]
+    st = torch.cuda.Stream()  # (a stream of this tool's: the route, the copy and the events around them all run on it)
+
+    def route_all():
+        return [prims[i].records_route(H, bufs[i], ns[i], outs[i], stream=st.cuda_stream, wait=False)[1] for i in range(G)]
+
+    def copy_all():
+        with torch.cuda.stream(st):
+            for i in range(G):
+                outs[i][:ns[i] * 64].copy_(bufs[i][:ns[i] * 64], non_blocking=True)
+
+    ms = {"route": [], "copy": []}
+    for run in range(8):  # a warm run of each, then 7 timed, alternating
+        for name, call in (("copy", copy_all), ("route", route_all)):  # (the route last: outs hold the pieces afterwards)
+            torch.cuda.synchronize()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record(st)
+            res = call()
+            ev[1].record(st)
+            torch.cuda.synchronize()
+            if run:
+                ms[name].append(ev[0].elapsed_time(ev[1]))
+    offs = res
+    out = {"workload": a.workload, "rows": a.rows, "records": a.records, "chunk": a.chunk, "shards": [G, H], "runs": 7,
+           "bytes": a.records * 64, "records_per_source": ns}
+    for name, v in ms.items():
+        out[name] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v),
+                     "gb_per_s_moved": a.records * 64 / (statistics.median(v) / 1e3) / 1e9}
+    out["route_over_copy"] = out["route"]["median_ms"] / out["copy"]["median_ms"]
+    # ---- the apply, destination by destination
+    # (log_entries bounds a pass, as for `fresh`: a small ring would cut the replay into passes of its size)
+    reps = [Engine(wl, n_rows=a.rows, log_entries=max(a.records, 1024), shard_index=j, shard_count=H, flags=_lib.FLAG_SHARD_REPLICA if H > 1 else 0)
+            for j in range(H)]
+    for e in reps:
+        e.populate(a.rows)
+        e.snapshot()
+    want = recovery.digest_sum(prims)
+    out["apply"], ok = {}, True
+    for name in ("unfolded", "folded"):
+        for run in ("warm", "timed"):
+            for e in reps:
+                e.restore()
+            torch.cuda.synchronize()
+            per, deferred = [0.0] * H, 0
+            for i in range(G):
+                for j in range(H):
+                    m = offs[i][j + 1] - offs[i][j]
+                    if not m:
+                        continue
+                    view = outs[i][64 * offs[i][j]:64 * offs[i][j + 1]]
+                    t0 = time.perf_counter()
+                    r = reps[j].log_apply_folded(view, m, a.chunk) if name == "folded" else reps[j].log_apply_device(view, m, a.chunk)
+                    per[j] += (time.perf_counter() - t0) * 1e3
+                    deferred += r.get("deferred_records", 0)
+        eq = recovery.digest_sum(reps) == want
+        ok = ok and eq
+        out["apply"][name] = {"per_shard_ms": per, "total_ms": sum(per), "records_per_s": a.records / (sum(per) / 1e3), "digests_equal": eq}
+        if name == "folded":
+            out["apply"][name]["deferred_records"] = deferred
+    print(json.dumps(out))
+    return 0 if ok else 1
 
 
 def child(a):
@@ -227,12 +338,17 @@ def main():
     ap.add_argument("--chunk", type=int, default=0, help="records per replay pass (0 = the replica's max_pass)")
     ap.add_argument("--timeout", type=int, default=540, help="seconds the GPU child may take")
     ap.add_argument("--fold", action="store_true", help="measure the folded replay against the unfolded one")
+    ap.add_argument("--shards", default="", help="G:H -- route G primary shards' logs to H replica shards and apply them")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.shards:
+        a.shards = tuple(int(x) for x in a.shards.split(":"))
+        assert len(a.shards) == 2 and 1 <= a.shards[0] <= 255 and 1 <= a.shards[1] <= 255, "--shards G:H, 1 .. 255 each"
     if a.child:
-        return child_fold(a) if a.fold else child(a)
+        return child_shards(a) if a.shards else child_fold(a) if a.fold else child(a)
     cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", "--workload", a.workload,
-           "--rows", str(a.rows), "--records", str(a.records), "--chunk", str(a.chunk)] + (["--fold"] if a.fold else [])
+           "--rows", str(a.rows), "--records", str(a.records), "--chunk", str(a.chunk)] + (["--fold"] if a.fold else []) + \
+          (["--shards", "%d:%d" % a.shards] if a.shards else [])
     return subprocess.run(cmd).returncode  # (124 / 137: the time limit; nothing else is started after a failure)
 
 

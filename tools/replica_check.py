@@ -2,7 +2,7 @@
 """Is a replica equal to its primary, what differs, and what does the repair cost -- on the device (dint_state_digest /
 dint_state_diff / dint_state_repair) next to the host way (dump_rows of both engines + a numpy compare).
 
-    tools/replica_check.py [--workload tatp|smallbank|both] [--rows N] [--repeats R] [--timeout S] [--blocks B]
+    tools/replica_check.py [--workload tatp|smallbank|both] [--rows N] [--repeats R] [--timeout S] [--blocks B] [--shards G]
 
 Per workload, two engines of N subscribers / accounts populated alike.  Printed as one JSON object:
   digest      milliseconds of one engine's digest (HIP events on the stream the kernels run on; min / median / max of R
@@ -18,6 +18,10 @@ Every device result is checked: the digests are equal again after each repair.
 two engines on one device with a `carry` that clones and counts: the block digest beside dint_state_digest and stream_rd, a replica
 1 % and 0.01 % behind -- blocks differing, bytes carried each way beside the image's bytes, the time beside the same-device diff +
 repair of an equal fall-behind -- and the 0.01 % case at B = 256, 4096 and 65536.
+
+--shards G: the pairwise resync of two shard SETS of G shards (recovery.resync_set; every engine created with
+DINT_FLAG_SHARD_REPLICA): the primaries take writes on 1 % of their rows, each shard its home rows; printed are the records and
+the wall-clock time per pair (with --blocks B: through the block path), and whether the two sets' digests add up equal afterwards.
 
 All GPU work happens in ONE child process under a time limit; the parent never opens the GPU."""
 import argparse
@@ -185,6 +189,45 @@ def child_blocks(a, workload):
     return 0 if out["ok"] else 1
 
 
+def child_shards(a, workload):
+    import numpy as np
+
+    from dint_amd import _lib, recovery, wire
+    from dint_amd.engine import Engine
+
+    tatp = workload == "tatp"
+    wl = wire.Workload.TATP if tatp else wire.Workload.SMALLBANK
+    G = a.shards
+
+    def shard_set():
+        out = [Engine(wl, n_rows=a.rows, log_entries=1 << 16, shard_index=i, shard_count=G, flags=_lib.FLAG_SHARD_REPLICA) for i in range(G)]
+        for e in out:
+            e.populate(a.rows)
+        return out
+
+    prims, reps = shard_set(), shard_set()
+    assert recovery.digest_sum(prims) == recovery.digest_sum(reps)
+    rng = np.random.default_rng(3)
+    changed = 0
+    for e in prims:  # new values for 1 % of every shard's own rows of table 0, with the versions they have
+        k, v, x = e.dump_rows(0)
+        pick = rng.choice(len(k), max(1, len(k) // 100), replace=False)
+        m = np.zeros(len(pick), wire.TATP_MSG if tatp else wire.SB_MSG)
+        m["type"], m["table"], m["key"] = (wire.Tatp.COMMIT_PRIM if tatp else wire.Sb.COMMIT_PRIM), 0, k[pick]
+        m["val"] = rng.integers(0, 256, m["val"].shape, dtype=np.uint8)
+        e.submit(m)
+        changed += len(pick)
+    t0 = time.perf_counter()
+    res = recovery.resync_set(prims, reps, blocks=a.blocks or None)
+    dt = time.perf_counter() - t0
+    out = {"workload": workload, "rows": a.rows, "shards": G, "blocks": a.blocks, "rows_changed": changed, "records": res["records"],
+           "per_shard": [{k: v for k, v in r.items()} for r in res["shards"]], "resync_ms": round(dt * 1e3, 3),
+           "digests_equal": res["digests_equal"], "runs": "one run"}
+    out["ok"] = bool(res["digests_equal"] and 0 < res["records"] <= changed)
+    print(json.dumps(out), flush=True)
+    return 0 if out["ok"] else 1
+
+
 def child(a, workload):
     import numpy as np
     import torch
@@ -316,16 +359,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--timeout", type=int, default=540, help="seconds the GPU child may take")
     ap.add_argument("--blocks", type=int, default=0, help="buckets per block: measure the block path (recovery.resync_blocks) instead")
+    ap.add_argument("--shards", type=int, default=0, help="G: the pairwise resync of two sets of G shards (recovery.resync_set)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     loads = ("tatp", "smallbank") if a.workload == "both" else (a.workload,)
     if a.child:
         for w in loads:
-            if rc := (child_blocks(a, w) if a.blocks else child(a, w)):
+            if rc := (child_shards(a, w) if a.shards else child_blocks(a, w) if a.blocks else child(a, w)):
                 return rc
         return 0
     cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", "--workload", a.workload,
-           "--rows", str(a.rows), "--repeats", str(a.repeats), "--blocks", str(a.blocks)]
+           "--rows", str(a.rows), "--repeats", str(a.repeats), "--blocks", str(a.blocks), "--shards", str(a.shards)]
     return subprocess.run(cmd).returncode  # (124 / 137: the time limit; nothing else is started after a failure)
 
 

@@ -34,6 +34,7 @@ SYMBOLS = [
     "dint_submit_segments_multi", "dint_submit_device_ahead", "dint_submit_segments_multi_ahead",
     "dint_log_drain_device", "dint_log_apply_device", "dint_log_apply_folded_device", "dint_state_digest", "dint_state_diff", "dint_state_repair",
     "dint_state_export", "dint_state_import", "dint_state_rehash", "dint_state_stats",
+    "dint_load_rows_device", "dint_populate_device",
     "dint_state_verify", "dint_state_compact",
     "dint_state_block_digest", "dint_state_block_select", "dint_state_block_rows", "dint_state_block_diff",
     "dint_records_route",
@@ -133,6 +134,16 @@ class ImageStats(C.Structure):
 
 class RehashTableStats(C.Structure):
     _fields_ = [("rows", C.c_uint64), ("overflow_entries", C.c_uint64), ("longest_chain", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class LoadTableStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("overflow_entries", C.c_uint64), ("longest_chain_entries", C.c_uint64), ("direct", C.c_uint64)]
+
+
+class LoadStats(C.Structure):
+    """dint_load_stats (include/dint_abi.h)"""
+    _fields_ = [("rows_loaded", C.c_uint64), ("foreign_rows", C.c_uint64), ("table", LoadTableStats * 5), ("direct", C.c_uint64),
+                ("temp_bytes", C.c_uint64), ("stage_ns", C.c_uint64 * 6), ("reserved", C.c_uint64 * 4)]
 
 
 class RehashStats(C.Structure):
@@ -305,6 +316,13 @@ def load() -> C.CDLL:
         "dint_records_route_tile": (u32, []),
         # ... and the rehash's layout rule (csrc/state_rehash.h) over keys in source order
         "dint_state_rehash_place_host": (i64, [vp, u64, u64, u32, u32, vp, vp, vp]),
+        # ... and the bulk load's rule (csrc/state_load.h): placement over a host view, the population's rows, its tile tables
+        "dint_load_rows_device": (C.c_int, [vp, u32, vp, vp, vp, u64, C.POINTER(LoadStats), vp]),
+        "dint_populate_device": (C.c_int, [vp, u64, C.POINTER(LoadStats), vp]),
+        "dint_state_load_place_host": (C.c_int, [vp, u32, vp, vp, vp, u64, C.POINTER(LoadStats)]),
+        "dint_populate_rows_host": (i64, [u32, u32, u64, u64, vp, vp, u64]),
+        "dint_populate_tile": (u32, []),
+        "dint_populate_tile_states_host": (i64, [u32, u32, u64, vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)  # AttributeError here = the .so does not export the ABI

@@ -353,6 +353,36 @@ bool dint_launch_rehash_plan(uint32_t t, const dint_kv *const *srcs, uint32_t n_
 void dint_launch_rehash_build(uint32_t t, const dint_kv &dst, uint64_t n, uint64_t row_at, uint64_t n_ent, uint32_t need,
                               const uint8_t *const *d_src_entries, dint_rehash_scratch s, hipStream_t st);
 
+// ---- bulk load (k_load.hip; state_load.h): rows in insertion order into a table that holds nothing, and the population's rows ----
+struct dint_load_scratch {
+  unsigned long long *words;  // [DINT_LOAD_WORDS] device words: the foreign rows, the plan's scan total = entries << 32 | overflow entries,
+                              // entries of the longest chain, (u32) bit 1: a bucket beyond KV_MAX_CHAIN entries
+  uint32_t *key_a, *idx_a;    // [n_max] unsorted keys / row numbers; after the sort the run heads / the buckets' row counts at the run heads
+  uint32_t *key_b, *idx_b;    // [n_max] sorted keys / row numbers
+  uint32_t *elist;            // [n_max] first rows of the entries
+  unsigned long long *scan;   // [n_max + 1] the scan of state_rehash.h
+  uint64_t n_max;
+  void *tmp;                  // the sort's and the scans' temporary storage
+  size_t tmp_bytes;
+};
+#define DINT_LOAD_WORDS 8u
+#define DINT_LOAD_FOREIGN_AT 0u
+#define DINT_LOAD_TOTAL_AT 1u
+#define DINT_LOAD_LONGEST_AT 2u
+#define DINT_LOAD_BAD_AT 4u
+int64_t dint_load_tmp_bytes(uint64_t n, uint64_t n_local, hipStream_t st);
+void dint_launch_load_count(const dint_kv &kv, uint32_t t, const uint64_t *d_keys, uint64_t n, dint_load_scratch s, hipStream_t st);
+bool dint_launch_load_plan(const dint_kv &kv, uint32_t t, const uint64_t *d_keys, uint64_t n, dint_load_scratch s, hipStream_t st, hipEvent_t *ev);
+// ... then (the host has compared the need with the pool) the table's entries
+void dint_launch_load_build(const dint_kv &kv, uint32_t t, const uint64_t *d_keys, const uint32_t *d_vers, const void *d_vals, uint64_t n, uint64_t n_ent,
+                            uint32_t need, dint_load_scratch s, hipStream_t st);
+void dint_launch_load_msgs(const dint_kv &kv, uint32_t t, const uint64_t *d_keys, const uint32_t *d_vers, const void *d_vals, uint64_t first, uint32_t m,
+                           void *d_req, hipStream_t st);
+// the tile table of a data-dependent group (state_load.h SL_G_AI / SL_G_SFCF) for n_subs subscribers, cached per process
+int dint_load_tiles(uint32_t group, uint32_t which, uint64_t n_subs, std::vector<uint64_t> *state, std::vector<uint64_t> *rows, uint64_t *total);
+void dint_launch_load_gen(uint32_t group, uint32_t which, uint64_t n_subs, const uint64_t *d_tile_state, const uint64_t *d_tile_rows, uint64_t *d_keys,
+                          void *d_vals, uint64_t cap, uint32_t val_size, hipStream_t st);
+
 // ---- multi-GPU routing (k_route.hip) --------------------------------------------------------------------------
 #define DINT_ROUTE_MAXW 64u        // ranks a batch can be routed to
 #define DINT_ROUTE_MAXN 1048576u   // requests per dint_route_pack call

@@ -5,10 +5,12 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <future>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -18,6 +20,7 @@
 #include "dint_kernels.h"
 #include "dint_kv.h"
 #include "dint_populate.h"
+#include "state_load.h"
 #include "state_rehash.h"
 #include "state_stats.h"
 
@@ -161,6 +164,11 @@ struct dint_engine {
   // rehash (dint_state_rehash, in the destination): scratch, grown on demand and kept; the events of its stage timing
   dint_rehash_scratch rehash{};
   hipEvent_t ev_rehash[4 + 4 * DINT_KV_MAX_TABLES] = {};
+  // bulk load (dint_load_rows_device / dint_populate_device): bit t of `fresh` = table t has taken nothing since creation / reset
+  // (whatever clears `blank` clears every bit; a direct load clears its table's); scratch, grown on demand; the stage events
+  uint32_t fresh = ~0u;
+  dint_load_scratch load{};
+  hipEvent_t ev_load[6] = {};
 
   // kv workloads (store / tatp / smallbank)
   dint_kv kv{};
@@ -422,7 +430,7 @@ int ahead_settle(dint_engine *e) {
 int run_pass(dint_engine *e, const void *d_req, uint32_t n, void *d_rep, hipStream_t st, int load_mode = 0,
              const dint_view &view = dint_flat_view(), bool inputs_ready = false, const dint_kv_ahead *next = nullptr) {
   bool part_done = false;
-  e->blank = false;
+  e->blank = false, e->fresh = 0;
   if (int rc = ahead_settle(e)) return rc;
   if (e->ahead.valid) {  // the pass that was announced, and nothing else
     if (e->ahead.req != d_req || e->ahead.rep != d_rep || e->ahead.n != n || view.seg_cap != e->ahead.seg_cap || load_mode) {
@@ -829,6 +837,39 @@ int rehash_alloc(dint_engine *e, uint32_t nb, uint64_t n_max, uint64_t n_all, si
   if (fresh) HIP_TRY(hipDeviceSynchronize());  // (the zero fills ran on the null stream: the engine's stream does not wait for it)
   return 0;
 }
+// bulk load scratch: the arrays grow to what a call needs and are kept (dint_populate_device frees them when it is done)
+void load_free(dint_engine *e) {
+  dint_load_scratch &s = e->load;
+  hipFree(s.words); hipFree(s.key_a); hipFree(s.idx_a); hipFree(s.key_b); hipFree(s.idx_b); hipFree(s.elist); hipFree(s.scan); hipFree(s.tmp);
+  s = dint_load_scratch{};
+}
+size_t load_scratch_bytes(const dint_load_scratch &s) { return (size_t)s.n_max * 28 + 8 + s.tmp_bytes; }
+int load_alloc(dint_engine *e, uint64_t n_max, size_t tmp_bytes) {
+  dint_load_scratch &s = e->load;
+  if (!s.words) {
+    if (int rc = dev_alloc((void **)&s.words, DINT_LOAD_WORDS * sizeof(unsigned long long))) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (the zero fill ran on the null stream: the engine's stream does not wait for it)
+  }
+  if (n_max > s.n_max) {
+    hipFree(s.key_a); hipFree(s.idx_a); hipFree(s.key_b); hipFree(s.idx_b); hipFree(s.elist); hipFree(s.scan);
+    s.key_a = s.idx_a = s.key_b = s.idx_b = s.elist = nullptr; s.scan = nullptr; s.n_max = 0;
+    int rc = dev_alloc((void **)&s.key_a, (size_t)n_max * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.idx_a, (size_t)n_max * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.key_b, (size_t)n_max * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.idx_b, (size_t)n_max * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.elist, (size_t)n_max * sizeof(uint32_t), false);
+    if (!rc) rc = dev_alloc((void **)&s.scan, (size_t)(n_max + 1) * sizeof(unsigned long long), false);
+    if (rc) return rc;
+    s.n_max = n_max;
+  }
+  if (tmp_bytes > s.tmp_bytes) {
+    hipFree(s.tmp);
+    s.tmp = nullptr; s.tmp_bytes = 0;
+    if (int rc = dev_alloc(&s.tmp, tmp_bytes, false)) return rc;
+    s.tmp_bytes = tmp_bytes;
+  }
+  return 0;
+}
 // the layout-relevant flags an image carries
 uint32_t image_flags(const dint_engine *e) { return e->cfg.workload == DINT_WL_TATP ? (e->cfg.flags & DINT_FLAG_LOCK_SAME_KEY) : 0u; }
 
@@ -1077,6 +1118,9 @@ void dint_engine_destroy(dint_engine_t *e) {
   dint_compact_free(e->tcompact);
   image_free(e);
   rehash_free(e);
+  load_free(e);
+  for (hipEvent_t ev : e->ev_load)
+    if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : e->ev_replay)
     if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : e->ev_fold)
@@ -1231,7 +1275,7 @@ int dint_submit_segments_multi_ahead(const dint_segments_item *items, uint32_t n
   for (uint32_t k = 0; k < n_items; k++) {
     const dint_segments_item &it = items[k];
     dint_engine *e = it.engine;
-    e->blank = false;
+    e->blank = false, e->fresh = 0;
     if (int rc = order_stream(e, st)) return rc;
     if (int rc = next_pass_seq(e, st)) return rc;
     pass[k].d_req = it.d_base; pass[k].d_rep = it.d_base; pass[k].n = it.n_seg * it.seg_cap;
@@ -1760,7 +1804,7 @@ int dint_log_apply_folded_device(dint_engine_t *e, const void *d_records, uint64
     if (w[0] > m || w[1] > m) return fail(DINT_EHIP, "log fold: counts beyond the chunk");
     if (timed) HIP_TRY(hipEventRecord(e->ev_fold[2], st));
     if (!dry && w[1]) {
-      e->blank = false;
+      e->blank = false, e->fresh = 0;
       // The fold wrote these records in ascending (table, bucket) order and names no table the workload has not, so the order
       // check cannot fail; its flag is collected with the repair's counts and read once, at the end of the call.
       dint_launch_state_repair_check(e->kv, f.repair, w[1], e->state, st);
@@ -1885,7 +1929,7 @@ int dint_state_verify(dint_engine_t *e, dint_table_verify *out, uint32_t cap_tab
   if (int rc = mark_stream(e, st)) return rc;
   uint64_t reclaimed = 0;
   const int rc = dint_verify_collect(e->kv, e->tverify, flags, st, out, &reclaimed);  // (the one synchronisation of the call)
-  if (reclaimed) e->blank = false;
+  if (reclaimed) e->blank = false, e->fresh = 0;
   if (timed && rc != DINT_EHIP)
     for (int k = 0; k < 3; k++) {
       float ms = 0;
@@ -2127,7 +2171,7 @@ int dint_state_repair(dint_engine_t *e, const void *d_records, uint64_t n, dint_
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = state_alloc(e, false)) return rc;
-  e->blank = false;
+  e->blank = false, e->fresh = 0;
   hipStream_t st = stream ? (hipStream_t)stream : e->stream;
   if (int rc = order_stream(e, st)) return rc;
   dint_launch_state_repair_check(e->kv, d_records, n, e->state, st);
@@ -2432,7 +2476,7 @@ int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n
   for (uint32_t t = 0; t < n_tables; t++)
     dint_launch_rehash_build(t, dst->kv, n_row[t], row_at[t], n_ent[t], (uint32_t)need[t], rs.src_entries + (size_t)t * SR_MAX_SRCS, rs, st);
   if (timed) HIP_TRY(hipEventRecord(ev[3], st));
-  dst->blank = false;
+  dst->blank = false, dst->fresh = 0;
   if (int rc = state_launched()) return done(rc);
   if (int rc = done(0)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
@@ -2509,7 +2553,7 @@ int dint_reset(dint_engine_t *e) {
   HIP_TRY(hipDeviceSynchronize());
   if (int rc = ahead_cancel(e)) return rc;
   for (auto &r : e->regions) HIP_TRY(hipMemset(r.first, 0, r.second));
-  e->blank = true;
+  e->blank = true, e->fresh = ~0u;
   e->pieces.clear();
   e->batches = e->requests = 0;
   e->log_drained = 0;
@@ -2554,7 +2598,7 @@ int dint_restore(dint_engine_t *e) {
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());
   if (int rc = ahead_cancel(e)) return rc;
-  e->blank = false;
+  e->blank = false, e->fresh = 0;
   for (size_t i = 0; i < e->regions.size(); i++)
     HIP_TRY(hipMemcpy(e->regions[i].first, e->snap[i], e->regions[i].second, hipMemcpyDeviceToDevice));
   HIP_TRY(hipDeviceSynchronize());
@@ -2583,6 +2627,185 @@ int dint_populate(dint_engine_t *e, uint64_t populate_n) {
                             [e](uint32_t table, const uint64_t *keys, const uint8_t *vals, uint64_t n) {
                               return load_rows_locked(e, table, keys, nullptr, vals, n);
                             });
+}
+
+namespace {
+
+uint64_t event_ns(hipEvent_t a, hipEvent_t b) {
+  float ms = 0;
+  return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (uint64_t)(ms * 1e6) : 0ull;
+}
+
+// n rows of device arrays into `table`, under the engine's mutex and behind state_quiet: directly where the table has taken
+// nothing, else as load-mode passes formed on the device.  extra_bytes: temporary memory the caller holds (the rows themselves)
+int load_device_locked(dint_engine *e, uint32_t table, const uint64_t *d_keys, const uint32_t *d_vers, const void *d_vals, uint64_t n,
+                       dint_load_stats *out, hipStream_t st, size_t extra_bytes) {
+  const bool direct = (e->fresh >> table & 1u) && e->pieces.empty();
+  const kv_tab &tb = e->kv.h.tab[table];
+  auto peak = [&]() {
+    if (out) out->temp_bytes = std::max<uint64_t>(out->temp_bytes, extra_bytes + load_scratch_bytes(e->load));
+  };
+  if (out) out->table[table].direct = direct;
+  if (!n) return 0;
+  if (!direct) {
+    if (out) out->direct = 0;
+    if (int rc = load_alloc(e, 0, 0)) return rc;
+    peak();
+    if (int rc = order_stream(e, st)) return rc;
+    dint_launch_load_count(e->kv, table, d_keys, n, e->load, st);
+    if (int rc = state_launched()) return rc;
+    for (uint64_t off = 0; off < n; off += e->pass_max) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(e->pass_max, n - off);
+      dint_launch_load_msgs(e->kv, table, d_keys, d_vers, d_vals, off, m, e->slot[0].d_req, st);
+      if (int rc = run_pass(e, e->slot[0].d_req, m, e->slot[0].d_req, st, 1)) return rc;
+      e->batches--;  // population passes are not request batches
+      e->requests -= m;
+    }
+    unsigned long long foreign = 0;
+    HIP_TRY(hipMemcpyAsync(&foreign, e->load.words + DINT_LOAD_FOREIGN_AT, sizeof foreign, hipMemcpyDeviceToHost, st));
+    if (int rc = mark_stream(e, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out) {
+      out->table[table].rows += n - foreign;
+      out->rows_loaded += n - foreign;
+      out->foreign_rows += foreign;
+    }
+    return 0;
+  }
+  if (tb.n_local >= 0xFFFFFFFFull) return fail(DINT_EINVAL, "table %u has %llu local buckets: the sort keys are 32-bit", table, (unsigned long long)tb.n_local);
+  const int64_t tmp = dint_load_tmp_bytes(n, tb.n_local, st);
+  if (tmp < 0) return fail(DINT_EHIP, "radix sort: temporary storage query failed");
+  if (int rc = load_alloc(e, n, (size_t)tmp)) return rc;
+  peak();
+  const bool timed = e->timer.on && out;
+  if (timed)
+    for (hipEvent_t &ev : e->ev_load)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  hipEvent_t *ev = e->ev_load;
+  if (int rc = order_stream(e, st)) return rc;
+  auto done = [&](int rc) {  // every way out after the first enqueue
+    if (int r = mark_stream(e, st)) return r;
+    return rc;
+  };
+  if (!dint_launch_load_plan(e->kv, table, d_keys, n, e->load, st, timed ? ev : nullptr)) return done(fail(DINT_EHIP, "radix sort or scan failed"));
+  if (int rc = state_launched()) return done(rc);
+  unsigned long long w[DINT_LOAD_WORDS];
+  HIP_TRY(hipMemcpyAsync(w, e->load.words, sizeof w, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t n_ent = w[DINT_LOAD_TOTAL_AT] >> 32, need = w[DINT_LOAD_TOTAL_AT] & 0xFFFFFFFFull;
+  if (out) {
+    out->table[table].overflow_entries = need;
+    out->table[table].longest_chain_entries = w[DINT_LOAD_LONGEST_AT];
+  }
+  if ((uint32_t)w[DINT_LOAD_BAD_AT] & 2u)
+    return done(fail(DINT_ESTATE, "a bucket of table %u would need more than %u overflow entries: nothing was written (a larger n_rows)", table, KV_MAX_CHAIN - 1u));
+  if (need > tb.pool_cap)
+    return done(fail(DINT_ENOMEM, "table %u needs %llu overflow entries, the pool has %u (dint_config.pool_entries); nothing was written", table,
+                     (unsigned long long)need, tb.pool_cap));
+  dint_launch_load_build(e->kv, table, d_keys, d_vers, d_vals, n, n_ent, (uint32_t)need, e->load, st);
+  if (timed) HIP_TRY(hipEventRecord(ev[4], st));
+  e->blank = false;
+  e->fresh &= ~(1u << table);
+  if (int rc = state_launched()) return done(rc);
+  if (int rc = done(0)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  if (out) {
+    out->table[table].rows += n - w[DINT_LOAD_FOREIGN_AT];
+    out->rows_loaded += n - w[DINT_LOAD_FOREIGN_AT];
+    out->foreign_rows += w[DINT_LOAD_FOREIGN_AT];
+    if (timed)
+      for (int k = 0; k < 4; k++) out->stage_ns[1 + k] += event_ns(ev[k], ev[k + 1]);
+  }
+  return 0;
+}
+
+}  // namespace
+
+int dint_load_rows_device(dint_engine_t *e, uint32_t table, const uint64_t *d_keys, const uint32_t *d_vers, const void *d_vals, uint64_t n,
+                          dint_load_stats *out, void *stream) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!e || (n && (!d_keys || !d_vals))) return fail(DINT_EINVAL, "null argument");
+  if (!e->kv.n_tables) return fail(DINT_ESTATE, "workload has no kv table");
+  if (table >= e->kv.n_tables) return fail(DINT_EINVAL, "bad table %u", table);
+  if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_vers & 3) || ((uintptr_t)d_vals & 7))
+    return fail(DINT_EINVAL, "keys and values need 8-byte aligned arrays, versions a 4-byte aligned one");
+  if (n > SR_MAX_ROWS) return fail(DINT_EINVAL, "%llu rows: at most %llu a call", (unsigned long long)n, (unsigned long long)SR_MAX_ROWS);
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  if (out) out->direct = 1;
+  return load_device_locked(e, table, d_keys, d_vers, d_vals, n, out, stream ? (hipStream_t)stream : e->stream, 0);
+}
+
+int dint_populate_device(dint_engine_t *e, uint64_t populate_n, dint_load_stats *out, void *stream) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!e) return fail(DINT_EINVAL, "null engine");
+  if (!e->kv.n_tables) return fail(DINT_ESTATE, "workload has no kv table");
+  if (populate_n > SR_MAX_ROWS / 12) return fail(DINT_EINVAL, "%llu subscribers: a table's rows must stay below 2^32 - 16", (unsigned long long)populate_n);
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  if (!e->blank || !e->pieces.empty())
+    return fail(DINT_ESTATE, "the engine is not blank: dint_reset it first (since creation or reset it has taken requests, rows, a log, a repair, a restore or an image)");
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  const uint32_t wl = e->cfg.workload, vs = e->kv.val_size;
+  if (out) out->direct = 1;
+  // the tile tables of the two data-dependent tatp groups, walked on another core while the device loads the tables that need none
+  struct Prepass { int rc = 0; uint64_t ns = 0; };
+  std::future<Prepass> pre;
+  if (wl == DINT_WL_TATP)
+    pre = std::async(std::launch::async, [populate_n]() {
+      Prepass p;
+      const auto t0 = std::chrono::steady_clock::now();
+      p.rc = dint_load_tiles(SL_G_AI, 0, populate_n, nullptr, nullptr, nullptr);
+      if (!p.rc) p.rc = dint_load_tiles(SL_G_SFCF, 0, populate_n, nullptr, nullptr, nullptr);
+      p.ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+      return p;
+    });
+  const bool timed = e->timer.on && out;
+  if (timed)
+    for (hipEvent_t &ev : e->ev_load)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  int rc = 0;
+  for (uint32_t t = 0; t < e->kv.n_tables && !rc; t++) {
+    uint32_t which;
+    const uint32_t group = sl_group(wl, t, &which);
+    uint64_t rows = populate_n * sl_rows_fixed(group);
+    std::vector<uint64_t> tile_state, tile_rows;
+    if (sl_draws(group) == SL_DRAWS_VAR) {
+      if (pre.valid()) {
+        const Prepass p = pre.get();
+        if (p.rc) { rc = fail(p.rc, "the tile table of the population could not be built"); break; }
+        if (out) out->stage_ns[5] = p.ns;
+      }
+      if ((rc = dint_load_tiles(group, which, populate_n, &tile_state, &tile_rows, &rows))) { rc = fail(rc, "the tile table of the population could not be built"); break; }
+    }
+    if (!rows) continue;
+    uint64_t *d_keys = nullptr, *d_tiles = nullptr;
+    void *d_vals = nullptr;
+    const size_t tile_bytes = tile_state.size() * 2 * sizeof(uint64_t), row_bytes = (size_t)rows * (8 + vs);
+    rc = dev_alloc((void **)&d_keys, (size_t)rows * 8, false);
+    if (!rc) rc = dev_alloc(&d_vals, (size_t)rows * vs, false);
+    if (!rc && tile_bytes) rc = dev_alloc((void **)&d_tiles, tile_bytes, false);
+    if (!rc && tile_bytes) {
+      hipError_t he = hipMemcpy(d_tiles, tile_state.data(), tile_bytes / 2, hipMemcpyHostToDevice);
+      if (he == hipSuccess) he = hipMemcpy(d_tiles + tile_state.size(), tile_rows.data(), tile_bytes / 2, hipMemcpyHostToDevice);
+      if (he != hipSuccess) rc = fail(DINT_EHIP, "hipMemcpy: %s", hipGetErrorString(he));
+    }
+    if (!rc) rc = order_stream(e, st);
+    if (!rc) {
+      if (timed) (void)hipEventRecord(e->ev_load[5], st);
+      dint_launch_load_gen(group, which, populate_n, d_tiles, d_tiles ? d_tiles + tile_state.size() : nullptr, d_keys, d_vals, rows, vs, st);
+      rc = state_launched();
+    }
+    if (!rc) rc = load_device_locked(e, t, d_keys, nullptr, d_vals, rows, out, st, row_bytes + tile_bytes);
+    if (!rc && timed) out->stage_ns[0] += event_ns(e->ev_load[5], e->ev_load[0]);
+    (void)hipStreamSynchronize(st);
+    hipFree(d_keys); hipFree(d_vals); hipFree(d_tiles);
+  }
+  if (pre.valid()) pre.wait();
+  load_free(e);
+  return rc;
 }
 
 int64_t dint_hash_size(dint_engine_t *e, uint32_t table) {

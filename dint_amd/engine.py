@@ -162,6 +162,40 @@ class Engine:
             vp = vers.ctypes.data
         _lib.check(self._L.dint_load_rows(self._h, table, keys.ctypes.data, vp, vals.ctypes.data, len(keys)))
 
+    # ---- bulk load on the device (dint_load_rows_device / dint_populate_device) --------------------------------
+    def _load_result(self, s, rc) -> dict:
+        d = {k: getattr(s, k) for k in ("rows_loaded", "foreign_rows", "direct", "temp_bytes")}
+        d["tables"] = [{k: getattr(s.table[t], k) for k in ("rows", "overflow_entries", "longest_chain_entries", "direct")}
+                       for t in range(_N_TABLES.get(self.workload, 0))]
+        d["stage_ns"] = dict(zip(("generate", "keys", "sort", "plan", "build", "prepass"), s.stage_ns))
+        self.last_load = d
+        _lib.check(rc)
+        return d
+
+    def load_rows_device(self, table: int, keys, vers, vals, stream: int = 0, n=None) -> dict:
+        """dint_load_rows_device: load_rows for torch DEVICE tensors -- keys (int64 / uint64 view, n), vers (int32, n, or None:
+        version 0), vals (uint8, n x val_size) -- in insertion order.  A table that has taken nothing since creation / reset is
+        built directly (csrc/state_load.h: what n kvs_insert calls leave, newest entry first); any other takes the rows as
+        load-mode passes formed on the device.  Returns {rows_loaded, foreign_rows, direct, temp_bytes, tables: [{rows,
+        overflow_entries, longest_chain_entries, direct}], stage_ns}, also kept in `last_load` -- as far as the call got when it
+        raises (the need per table after DINT_ENOMEM: nothing was written then).  With `n` given, keys / vers / vals may be
+        raw device addresses."""
+        if n is None:
+            n = int(keys.numel())
+            assert keys.is_contiguous() and vals.is_contiguous() and keys.element_size() == 8 and vals.numel() == n * self.val_size
+            assert vers is None or (vers.is_contiguous() and vers.element_size() == 4 and vers.numel() == n)
+        s = _lib.LoadStats()
+        rc = self._L.dint_load_rows_device(self._h, table, _ptr(keys), None if vers is None else _ptr(vers), _ptr(vals), n, C.byref(s), stream)
+        return self._load_result(s, rc)
+
+    def populate_device(self, populate_n: int, stream: int = 0) -> dict:
+        """dint_populate_device: populate() without the host -- the reference's rows of the first populate_n subscribers /
+        accounts generated on the device table by table and loaded directly.  The engine must be blank.  Result as
+        load_rows_device's, summed over the tables."""
+        s = _lib.LoadStats()
+        rc = self._L.dint_populate_device(self._h, populate_n, C.byref(s), stream)
+        return self._load_result(s, rc)
+
     def hash_size(self, table: int) -> int:
         return _lib.check(self._L.dint_hash_size(self._h, table))
 

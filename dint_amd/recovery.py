@@ -322,6 +322,26 @@ def rehash(src_engines, dst_engines, drop_locks: bool = False) -> dict:
     return tot
 
 
+def populate_set(engines, n: int) -> dict:
+    """The reference's population of the first n subscribers / accounts into a shard set of BLANK engines without the host
+    (Engine.populate_device): every engine generates all rows on its device and keeps the ones that are home to it.  With a
+    complete set (shard j of H at position j) every row lands exactly once; this is checked -- each row is loaded by one engine
+    and foreign to the H - 1 others -- and DintError is raised otherwise.  Returns {rows_loaded, temp_bytes: the largest peak,
+    tables: per table {rows, overflow_entries, longest_chain_entries} over the set, per_engine: [Engine.last_load]}."""
+    engines = list(engines)
+    per = [e.populate_device(n) for e in engines]
+    tot = {"rows_loaded": sum(p["rows_loaded"] for p in per), "temp_bytes": max([p["temp_bytes"] for p in per] or [0]),
+           "per_engine": per, "tables": []}
+    for t in range(len(per[0]["tables"]) if per else 0):
+        tot["tables"].append({"rows": sum(p["tables"][t]["rows"] for p in per),
+                              "overflow_entries": sum(p["tables"][t]["overflow_entries"] for p in per),
+                              "longest_chain_entries": max(p["tables"][t]["longest_chain_entries"] for p in per)})
+    if per and sum(p["foreign_rows"] for p in per) != (len(per) - 1) * tot["rows_loaded"]:
+        raise DintError(f"populate_set: {tot['rows_loaded']} rows loaded by {len(per)} engines, {sum(p['foreign_rows'] for p in per)} "
+                        "found foreign: not a complete shard set")
+    return tot
+
+
 def digest_sum(engines) -> list:
     """the digests of a set of engines added up per table: rows and sum add, xr xors (Engine.state_digest)"""
     out = None

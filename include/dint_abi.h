@@ -552,6 +552,46 @@ typedef struct dint_rehash_stats {
 } dint_rehash_stats;
 int dint_state_rehash(dint_engine_t *dst, dint_engine_t *const *srcs, uint32_t n_srcs, uint32_t flags, dint_rehash_stats *out,
                       void *stream);
+
+/* ---- bulk load (v5, additive): rows loaded and the population generated -- on the device ---------------------------------
+ * dint_load_rows_device is dint_load_rows for DEVICE arrays: keys[n] (8-byte aligned), vers[n] (4-byte aligned; NULL: version
+ * 0), vals[n][val_size] (8-byte aligned), n < 2^32 - 16, rows in insertion order.  The tables afterwards are what n kvs_insert
+ * calls in that order leave (dint_amd/csrc/state_load.h is the rule): rows home to another shard are skipped and counted,
+ * duplicate keys are rows like any other, chains run newest entry first.
+ *   A table that has taken nothing since dint_engine_create / dint_reset is built DIRECTLY: hash, stable sort by local bucket,
+ *   scan of the overflow entries, one host synchronisation to compare the need with the pool, then every entry written whole
+ *   by one lane group.  Overflow entries are pool 0 .. need - 1 in (bucket, insertion) order, pool_top takes one store, lock
+ *   bytes / owner keys / smallbank counters are not written.  Refused with nothing written: DINT_ENOMEM when the table needs
+ *   more overflow entries than the pool has (out->table[t].overflow_entries is the need, as dint_state_rehash reports it);
+ *   DINT_ESTATE when a bucket would need more than 4095 overflow entries.  The table stops being untouched, the engine blank.
+ *   Any other table takes the rows as load-mode passes formed on the device from the arrays: result and refusals are
+ *   dint_load_rows's (out->direct = 0; overflow_entries and longest_chain_entries are not known then and stay 0).
+ * DINT_EINVAL: a null or misaligned array, a bad table, n too large.  DINT_ESTATE: a workload without kv tables, a batch announced
+ * by dint_submit_device_ahead pending.  Synchronous; runs on `stream` (NULL = the engine's own) behind the engine's pending work.
+ *
+ * dint_populate_device is dint_populate without the host: table by table the reference's rows for the first populate_n
+ * subscribers / accounts are generated on the device in insertion order and loaded directly.  The engine must be blank
+ * (DINT_ESTATE otherwise); a sharded engine generates everything and keeps its home rows.  Temporary device memory is one
+ * table's rows and plan at a time, freed before the call returns; out->temp_bytes is the peak.  A refusal of a table's load
+ * leaves that table and the ones behind it empty, the ones before it loaded. */
+typedef struct dint_load_stats {
+  uint64_t rows_loaded;  /* rows home to this engine */
+  uint64_t foreign_rows; /* rows home to another shard (skipped) */
+  struct {
+    uint64_t rows;                  /* home rows of the table */
+    uint64_t overflow_entries;      /* the table's need (direct loads; also when refused) */
+    uint64_t longest_chain_entries; /* entries of its longest chain, the inline entry included (direct loads) */
+    uint64_t direct;                /* 1: built directly, 0: loaded by passes (or not loaded by this call) */
+  } table[5];
+  uint64_t direct;      /* 1: every table this call loaded was built directly */
+  uint64_t temp_bytes;  /* peak temporary device memory of the call */
+  uint64_t stage_ns[6]; /* with dint_timing_enable: generate, keys, sort, plan, build between events, summed over the tables; [5] the
+                           host pre-pass of the data-dependent tatp tables (0 when the process had it cached) */
+  uint64_t reserved[4];
+} dint_load_stats;
+int dint_load_rows_device(dint_engine_t *e, uint32_t table, const uint64_t *d_keys, const uint32_t *d_vers, const void *d_vals, uint64_t n,
+                          dint_load_stats *out, void *stream);
+int dint_populate_device(dint_engine_t *e, uint64_t populate_n, dint_load_stats *out, void *stream);
 /* ---- table report (v5, additive): occupancy and chain shape of an engine's tables -- read where they lie ----------------
  * What tells an operator WHEN to rehash: how full the buckets are, how long the chains, how much of the overflow pool is
  * linked, how many slots are holes or shadowed duplicates, whether lock words are held (dint_state_rehash refuses those).

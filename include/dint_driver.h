@@ -299,6 +299,24 @@ int64_t dint_state_block_rows_host(const dint_tables_view *view, uint64_t block_
 int64_t dint_state_block_diff_host(const dint_tables_view *view, uint64_t block_buckets, const uint32_t *ids, uint32_t n_ids, const void *rows,
                                    uint64_t n_rows, void *records, uint64_t cap, struct dint_diff_stats *out_stats);
 
+/* ---- bulk load: the rule over caller-provided memory (dint_amd/csrc/state_load.h) -----------------------------------------------
+ * dint_state_load_place_host: the direct load of dint_load_rows_device (include/dint_abi.h) into table `table` of a view in HOST
+ * memory (the view and its check of the verify forms above), which must hold nothing: keys / vers (may be NULL) / vals[n][val_size]
+ * in insertion order.  Return value, refusals (DINT_ENOMEM, DINT_ESTATE: not a byte written) and `out` are the device call's.
+ * dint_populate_rows_host: the rows that subscribers / accounts first .. first + count - 1 add to `table` of the reference's
+ * population of `workload`, in insertion order, through the rule the generation kernels run; returns their number (also when it
+ * exceeds cap: only cap rows are written), or DINT_EINVAL.  vals: 40 bytes per row, 8 for smallbank.
+ * dint_populate_tile: subscribers per workgroup of the generation kernels.  dint_populate_tile_states_host: the tile table of a
+ * data-dependent table (tatp 2, 3, 4; any other: DINT_ESTATE) for n_subs subscribers -- state[k] = fastrand's state at subscriber
+ * k * tile, rows[k] = the table's rows of the subscribers before it, k = 0 .. n_subs / tile; returns the entries (only cap are
+ * written).  The table is computed once per process and continued to the largest n seen.  No device call in any of them. */
+struct dint_load_stats; /* include/dint_abi.h */
+int dint_state_load_place_host(const dint_tables_view *view, uint32_t table, const uint64_t *keys, const uint32_t *vers, const void *vals,
+                               uint64_t n, struct dint_load_stats *out);
+int64_t dint_populate_rows_host(uint32_t workload, uint32_t table, uint64_t first, uint64_t count, uint64_t *keys, void *vals, uint64_t cap);
+uint32_t dint_populate_tile(void);
+int64_t dint_populate_tile_states_host(uint32_t workload, uint32_t table, uint64_t n_subs, uint64_t *state, uint64_t *rows, uint64_t cap);
+
 /* ---- record routing: the rule over caller-provided memory (dint_amd/csrc/state_route.h) ----------------------------------------
  * dint_records_route (include/dint_abi.h) over a list in HOST memory, at any alignment: the stable partition of the n 64-byte records
  * at rec by home shard -- (fasthash64(key) % the table's bucket count) % dst_count, the bucket counts those of an engine of

@@ -292,6 +292,8 @@ def load() -> C.CDLL:
         "dint_state_compact": (C.c_int, [vp, C.POINTER(TableCompact), u32, u32, vp]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
+        # ... and the log ring's words under announcements, cancels and drains (csrc/log_ring.h)
+        "dint_log_ring_host": (i64, [u32, vp, u32, vp, u64]),
         "dint_log_fold_host": (i64, [u32, u32, vp, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(FoldStats)]),
         # ... and the state sync's rules (csrc/state_sync.h) over dumped rows
         "dint_state_row_hash_host": (u64, [u64, u32, u32, vp, u32]),

@@ -22,10 +22,16 @@ struct dint_dev_stats {
 // the resolve stage -- three times (pass number % 3).  What only the resolve / hot / late stages of one pass touch (ovf, ovf2,
 // bigq, hotpub, lateq, bigrdy) exists once: those stages of two passes never overlap.
 #define DINT_KV_CTL_WORDS 64u  // words of one set of control words: two 128-byte lines
+// what the partition stage of a pass leaves for a cancel of its announcement (engine.hip, ahead_cancel): the pass's log records,
+// and what it added to dint_dev_stats::bad_requests / foreign_requests
+#define DINT_KV_CTL_LOGN 37u
+#define DINT_KV_CTL_BAD 38u
+#define DINT_KV_CTL_FOREIGN 39u
 struct dint_kv_sets {
   uint32_t *ctl[3] = {nullptr, nullptr, nullptr};   // [DINT_KV_CTL_WORDS] {[0] records handed to the big-sub path, [1] overflow-list entries, [2] tiles handed
                                                     // out, [3] work items listed, [4] item tickets, [5] late items, [6] coarse bins that have listed,
-                                                    // on the second line: [32 .. 36] INSERT requests per table (k_kv_dev.h KV_CTL_INS)}
+                                                    // on the second line: [32 .. 36] INSERT requests per table (k_kv_dev.h KV_CTL_INS), [37 .. 39]
+                                                    // DINT_KV_CTL_LOGN / _BAD / _FOREIGN}
   uint32_t *pub[3] = {nullptr, nullptr, nullptr};   // [1024] log requests per tile of the partition, bit 31 = published
   uint32_t *bin_cnt[2] = {nullptr, nullptr};        // [DINT_KV_CMAX] records per coarse bin
   uint4 *kbins[2] = {nullptr, nullptr};             // [C][cap] the coarse bins

@@ -20,6 +20,7 @@
 #include "dint_kernels.h"
 #include "dint_kv.h"
 #include "dint_populate.h"
+#include "log_ring.h"
 #include "state_load.h"
 #include "state_rehash.h"
 #include "state_stats.h"
@@ -132,6 +133,7 @@ struct dint_engine {
   // log
   dint_log log{};
   uint64_t log_drained = 0;  // records handed out (or given up as lost) by dint_log_drain
+  uint64_t log_gone = 0;     // ... of them, lost to a cancelled announcement's records and not yet reported (log_ring.h)
   uint64_t snap_log_drained = 0;  // ... when the snapshot was taken (dint_restore puts it back)
   // log replay (dint_log_apply_device): scratch of one chunk, allocated on first use; the events of its stage timing
   dint_replay_scratch replay{};
@@ -289,7 +291,7 @@ int next_pass_seq(dint_engine *e, hipStream_t st) {
 // kv engines: the log's ring position after the last pass lives in tail[(passes + 1) & 1] -- the partition of pass p reads
 // tail[p & 1] and writes tail[(p + 1) & 1], because it may run beside the resolve stage of pass p - 1 (k_kv_pass), which used to
 // copy one word onto the other.  dint_snapshot / dint_restore / dint_reset leave both words equal.
-int log_cur(const dint_engine *e) { return e->kv.n_tables ? (int)((e->scratch.kvs.pass_no + 1) & 1) : 1; }
+int log_cur(const dint_engine *e) { return e->kv.n_tables ? (int)lg_cur(e->scratch.kvs.pass_no) : 1; }
 
 // one pass (n <= pass_max) on device buffers
 // scratch sets 1 .. of the lock pipe: what k_lock_count / k_kv_scan_place / k_lock_resolve share within one pass
@@ -386,8 +388,10 @@ int run_lock_pass_piped(dint_engine *e, const void *d_req, uint32_t n, void *d_r
 
 // An announced batch (dint_submit_device_ahead) that will not be submitted after all: its partition stage has filled the
 // coarse bins and the control words of the next pass -- drain the GPU and leave the pass scratch as between passes.  What
-// the stage wrote outside the scratch stays: the announced batch's log records (the ring is about to be restored or reset
-// by the callers that cancel silently; the others report DINT_ESTATE).
+// the stage wrote outside the scratch is taken back too (include/dint_abi.h: the engine is as if it had never seen the batch):
+// the log's tail, appended count and drain cursor (log_ring.h, lg_cancel) and the bad / foreign requests it counted into
+// dint_stats -- by the counts the partition left in the announced pass's control words (DINT_KV_CTL_LOGN ..).  The ring slots
+// from the tail on keep the batch's records: the one thing that stays.
 int ahead_cancel(dint_engine *e) {
   if (!e->ahead.valid) return 0;
   e->ahead.valid = false;
@@ -403,17 +407,32 @@ int ahead_cancel(dint_engine *e) {
     return 0;
   }
   dint_scratch &s = e->scratch;
+  // what the cancelled partition counted, before its control words are cleared: {log records, bad requests, foreign requests}
+  // (the announced pass is number pass_no + 1: it was never launched)
+  uint32_t cnt[3];
+  static_assert(DINT_KV_CTL_BAD == DINT_KV_CTL_LOGN + 1 && DINT_KV_CTL_FOREIGN == DINT_KV_CTL_LOGN + 2, "three words in a row");
+  HIP_TRY(hipMemcpy(cnt, s.kvs.ctl[(s.kvs.pass_no + 1) % 3] + DINT_KV_CTL_LOGN, sizeof cnt, hipMemcpyDeviceToHost));
   for (int k = 0; k < 2; k++) HIP_TRY(hipMemset(s.kvs.bin_cnt[k], 0, DINT_KV_PMAX * sizeof(uint32_t)));
   HIP_TRY(hipMemset(s.kvs.ctl[0], 0, 3 * DINT_KV_CTL_WORDS * sizeof(uint32_t)));
   HIP_TRY(hipMemset(s.kvs.pub[0], 0, 3 * 1024 * sizeof(uint32_t)));
   if (e->log.tail) {  // the tail the cancelled partition published is not the current one
     uint32_t t[4];
     HIP_TRY(hipMemcpy(t, e->log.tail, sizeof t, hipMemcpyDeviceToHost));
-    const int c = log_cur(e);  // (the cancelled pass was never counted: `c` is the word it read, c ^ 1 the one it wrote)
-    uint64_t appended = (uint64_t)t[2] | ((uint64_t)t[3] << 32);
-    appended -= std::min<uint64_t>(appended, (t[c ^ 1] + e->log.cap - t[c]) % e->log.cap);
-    t[c ^ 1] = t[c]; t[2] = (uint32_t)appended; t[3] = (uint32_t)(appended >> 32);
+    const uint32_t c = (uint32_t)log_cur(e);  // (the cancelled pass was never counted: `c` is the word it read, c ^ 1 the one it wrote)
+    LgRing r = {{t[0], t[1]}, (uint64_t)t[2] | ((uint64_t)t[3] << 32), e->log_drained, e->log_gone};
+    lg_cancel(r, c, cnt[0], e->log.cap);
+    t[0] = r.tail[0]; t[1] = r.tail[1]; t[2] = (uint32_t)r.appended; t[3] = (uint32_t)(r.appended >> 32);
+    e->log_drained = r.drained; e->log_gone = r.gone;
     HIP_TRY(hipMemcpy(e->log.tail, t, sizeof t, hipMemcpyHostToDevice));
+  }
+  if (cnt[1] || cnt[2]) {  // (rare: malformed requests, requests of another shard)
+    unsigned long long v[2];
+    HIP_TRY(hipMemcpy(&v[0], &s.stats->bad_requests, sizeof v[0], hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&v[1], &s.stats->foreign_requests, sizeof v[1], hipMemcpyDeviceToHost));
+    v[0] -= std::min<unsigned long long>(v[0], cnt[1]);
+    v[1] -= std::min<unsigned long long>(v[1], cnt[2]);
+    HIP_TRY(hipMemcpy(&s.stats->bad_requests, &v[0], sizeof v[0], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(&s.stats->foreign_requests, &v[1], sizeof v[1], hipMemcpyHostToDevice));
   }
   HIP_TRY(hipDeviceSynchronize());  // (the fills ran on the null stream: the engine's streams do not wait for it)
   return 0;
@@ -436,14 +455,21 @@ int run_pass(dint_engine *e, const void *d_req, uint32_t n, void *d_rep, hipStre
     if (e->ahead.req != d_req || e->ahead.rep != d_rep || e->ahead.n != n || view.seg_cap != e->ahead.seg_cap || load_mode) {
       if (int rc = ahead_cancel(e)) return rc;
       return fail(DINT_ESTATE, "the batch announced by dint_submit_device_ahead (%u requests at %p) must be the engine's next "
-                               "submission; its log records are appended already", e->ahead.n, e->ahead.req);
+                               "submission; the announcement is cancelled", e->ahead.n, e->ahead.req);
     }
     e->ahead.valid = false;
     e->ahead.broken.reset();
     part_done = true;
   }
   if (int rc = order_stream(e, st)) return rc;
-  const bool piped = inputs_ready && n && !e->timer.on && (e->cfg.workload == DINT_WL_FASST || e->cfg.workload == DINT_WL_2PL);
+  bool piped = inputs_ready && n && !e->timer.on && (e->cfg.workload == DINT_WL_FASST || e->cfg.workload == DINT_WL_2PL);
+  if (piped && part_done) {
+    // the pass was announced by one that was not piped (kernel timing was on then): its count stage has run, into e->ahead.set.
+    // The piped path would count it again, into a set of its own rotation -- after one earlier piped pass the same set.  This
+    // pass resolves from the set it was counted into, on one stream, and announces nothing: the next one is piped again.
+    piped = false;
+    next = nullptr;
+  }
   if (!piped) e->lp.after_serial = true;
   static const char *const lock_names[] = {"k_lock_count", "k_kv_scan_place", "k_lock_resolve"};
   static const char *const log_names[] = {"k_log_append"};
@@ -880,17 +906,11 @@ int64_t log_drain_locked(dint_engine *e, void *records, uint64_t cap, uint64_t *
   HIP_TRY(hipDeviceSynchronize());
   uint32_t t[4];
   HIP_TRY(hipMemcpy(t, e->log.tail, sizeof t, hipMemcpyDeviceToHost));
-  const uint64_t total = (uint64_t)t[2] | ((uint64_t)t[3] << 32);
-  if (e->log_drained > total) e->log_drained = total;  // the engine was reset / restored to an earlier state
-  uint64_t pending = total - e->log_drained, gone = 0;
-  if (pending > e->log.cap) {  // the ring lapped the reader: the oldest records are overwritten
-    gone = pending - e->log.cap;
-    pending = e->log.cap;
-  }
-  if (lost) *lost = gone;
-  e->log_drained += gone;
-  const uint64_t n = std::min<uint64_t>(pending, cap);
-  uint64_t pos = e->log_drained % e->log.cap;  // record k of the stream lives at ring slot k % cap
+  LgRing r = {{t[0], t[1]}, (uint64_t)t[2] | ((uint64_t)t[3] << 32), e->log_drained, e->log_gone};
+  const LgDrain d = lg_drain(r, e->log.cap, cap);  // (log_ring.h: the cursor, what the ring lapped, where the records start)
+  if (lost) *lost = d.lost;
+  const uint64_t n = d.n;
+  uint64_t pos = d.pos;  // record k of the stream lives at ring slot k % cap
   uint8_t *out = (uint8_t *)records;
   for (uint64_t done = 0; done < n;) {
     const uint64_t run = std::min<uint64_t>(n - done, e->log.cap - pos);
@@ -900,7 +920,7 @@ int64_t log_drain_locked(dint_engine *e, void *records, uint64_t cap, uint64_t *
     pos = (pos + run) % e->log.cap;
   }
   if (to_device && n) HIP_TRY(hipStreamSynchronize(st));  // the records are complete when the call returns
-  e->log_drained += n;
+  e->log_drained = r.drained; e->log_gone = r.gone;
   return (int64_t)n;
 }
 
@@ -1674,6 +1694,13 @@ int64_t dint_log_drain_device(dint_engine_t *e, void *d_records, uint64_t cap, u
   if (!e->log.ring) return fail(DINT_ESTATE, "workload has no log");
   std::lock_guard<std::mutex> lk(e->mu);
   return log_drain_locked(e, d_records, cap, lost, true, stream ? (hipStream_t)stream : e->stream);
+}
+
+// the ring's words and the drain cursor under passes, announcements, cancels and drains, on the host (include/dint_driver.h): the
+// log_ring.h functions ahead_cancel, log_drain_locked and the partition stage call
+int64_t dint_log_ring_host(uint32_t cap, const uint32_t *ops, uint32_t n_ops, uint64_t *out, uint64_t out_cap) {
+  const int64_t w = lg_walk(cap, ops, n_ops, out, out_cap);
+  return w < 0 ? fail(DINT_EINVAL, "dint_log_ring_host: a bad op, a sequence no engine allows, or out too small") : w;
 }
 
 // one chunk of dint_log_apply_device: m <= e->replay.cap records at d_rec, everything enqueued on st; the acks are counted
@@ -2556,7 +2583,7 @@ int dint_reset(dint_engine_t *e) {
   e->blank = true, e->fresh = ~0u;
   e->pieces.clear();
   e->batches = e->requests = 0;
-  e->log_drained = 0;
+  e->log_drained = e->log_gone = 0;
   e->pool_seen = 0;
   e->h_pool[0] = e->h_pool[1] = 0;
   HIP_TRY(hipDeviceSynchronize());
@@ -2604,6 +2631,7 @@ int dint_restore(dint_engine_t *e) {
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(e->h_pool, &e->scratch.stats->pool_exhausted, sizeof(unsigned long long), hipMemcpyDeviceToHost));
   e->pool_seen = e->h_pool[1] = *e->h_pool;
+  e->log_gone = 0;
   e->log_drained = e->snap_log_drained;  // the drain cursor belongs to the log's history
   return 0;
 }

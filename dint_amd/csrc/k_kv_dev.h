@@ -14,6 +14,7 @@
 #include "dint_kv.h"
 #define KVB_SORT_INLINE
 #include "dint_bins.h"
+#include "log_ring.h"
 
 // ---- wire formats ------------------------------------------------------------------------------------
 template <int WL> struct Fmt;
@@ -91,6 +92,9 @@ __device__ static inline void kv_dev_pend_set(kv_dev &Skv, uint32_t pno) {
 // tatp bench stream 3,040 -> 2,700 Mtxn/s; on a line of their own: as without the load).
 #define KV_CTL_INS 32u  // control words [32 .. 32 + DINT_KV_MAX_TABLES): INSERT requests of the pass per table (dint_kv_sets::ctl)
 static_assert(KV_CTL_INS + DINT_KV_MAX_TABLES <= DINT_KV_CTL_WORDS && KV_CTL_INS * 4 >= 128, "a set of control words is DINT_KV_CTL_WORDS; the counts on a line of their own");
+// ... and behind them the three words a cancelled announcement is undone by (dint_kernels.h DINT_KV_CTL_LOGN / _BAD / _FOREIGN)
+#define KV_CTL_END (DINT_KV_CTL_FOREIGN + 1u)
+static_assert(DINT_KV_CTL_LOGN == KV_CTL_INS + DINT_KV_MAX_TABLES && KV_CTL_END <= DINT_KV_CTL_WORDS, "the cancel's words follow the INSERT counts");
 __device__ static inline uint32_t kv_dev_word(const kv_dev *kv, const uint32_t *ctl, uint32_t w) {
   constexpr uint32_t at = (uint32_t)(offsetof(kv_dev, pass_ins) / 4);
   return w >= at && w < at + DINT_KV_MAX_TABLES ? ctl[KV_CTL_INS + w - at] : ((const uint32_t *)kv)[w];
@@ -273,7 +277,10 @@ __device__ __forceinline__ static void kv_part_body(const kv_pass_args &A, kv_pa
     live = live && idx[j] < n;
     r[j] = kv_read_request<WL>(req + moff[j], live, kv, A.load_mode);
     lm[j] = __ballot(r[j].cls == 2);
-    if (live && !r[j].cls) atomicAdd(&A.stats->bad_requests, 1ULL);
+    if (live && !r[j].cls) {  // (counted for the pass too: a cancelled announcement takes it back, engine.hip ahead_cancel)
+      atomicAdd(&A.stats->bad_requests, 1ULL);
+      atomicAdd(&A.big[DINT_KV_CTL_BAD], 1u);
+    }
   }
   // log requests of this tile: publish the count at once (tatp / smallbank)
   if (WL != DINT_WL_STORE) {
@@ -318,7 +325,10 @@ __device__ __forceinline__ static void kv_part_body(const kv_pass_args &A, kv_pa
       bool mine = true;
       if (kv->shard_count > 1) {
         mine = (uint32_t)(g % kv->shard_count) == kv->shard_index;
-        if (!mine && !A.load_mode) atomicAdd(&A.stats->foreign_requests, 1ULL);
+        if (!mine && !A.load_mode) {
+          atomicAdd(&A.stats->foreign_requests, 1ULL);
+          atomicAdd(&A.big[DINT_KV_CTL_FOREIGN], 1u);
+        }
         local = (uint32_t)(g / kv->shard_count);
       }
       if (mine) {
@@ -387,8 +397,9 @@ __device__ __forceinline__ static void kv_part_body(const kv_pass_args &A, kv_pa
     const uint32_t tw = A.pno & 1u;  // the ring position before this pass: tail[pno], after it: tail[pno ^ 1] (engine.hip, log_cur)
     if (tile == A.n_tiles - 1 && t == 0) {
       const uint32_t total = base + tile_total;
-      log.tail[tw ^ 1u] = (uint32_t)(((uint64_t)log.tail[tw] + total) % log.cap);
+      log.tail[tw ^ 1u] = lg_tail_after(log.tail[tw], total, log.cap);
       *(unsigned long long *)(log.tail + 2) += total;  // records ever appended (dint_log_drain)
+      A.big[DINT_KV_CTL_LOGN] = total;  // ... by this pass: what a cancelled announcement takes back (log_ring.h, lg_cancel)
     }
 #pragma unroll
     for (int j = 0; j < RPT; j++) {
@@ -2679,7 +2690,7 @@ __device__ __forceinline__ static void kv_resolve_role(const kv_pass_args &A, ui
     L.hist[t] = 0; L.cur[t] = 0; L.cflag[t] = 0;
   }
   if (b == 0) {  // the control words of the pass AFTER NEXT: the next pass's partition may be running beside this workgroup (k_kv_pass)
-    if (t < 16 || (t >= KV_CTL_INS && t < KV_CTL_INS + DINT_KV_MAX_TABLES)) A.big_z[t] = 0;
+    if (t < 16 || (t >= KV_CTL_INS && t < KV_CTL_END)) A.big_z[t] = 0;
     for (uint32_t k = t; k < 1024; k += NT) A.blk_pub_z[k] = 0;
   }
   __syncthreads();

@@ -216,12 +216,29 @@ int dint_submit_device(dint_engine_t *e, const void *d_reqs, uint32_t n, void *d
  * overlap this call's.  The engine then runs the next batch's table-free first stage (classify, hash, partition into the
  * pass's coarse bins, and the log appends of its COMMIT_LOG / DELETE_LOG requests) in the SAME kernel launch as this batch's
  * hot keys (k_kv_hot_part) and starts the next call at its resolve kernel: a pass's chain is two launches instead of four.
- * Replies, table state and log ring are exactly those of two plain calls; between the two calls dint_read_log /
- * dint_log_drain already show the announced batch's log records.  A different next submission (or dint_snapshot) fails
- * with DINT_ESTATE after the engine has cleaned its scratch -- the announced batch's log records stay where they are, and
- * its reply buffer (= its request buffer, when in place) holds what the first stage wrote: undefined for the caller;
- * dint_reset / dint_restore drop the announcement silently.  lock_fasst / lock_2pl (batches of at most 65,536): the count
- * stage of the next batch rides in this batch's resolve launch the same way (k_lock_pass).  A dint_submit_device of more requests than one pass takes looks
+ * Replies, table state and log ring are exactly those of two plain calls.
+ * Between the two calls (tatp / smallbank): the ring holds the announced batch's log records already, and dint_log_drain /
+ * dint_log_drain_device hand them out with the rest; the tail dint_read_log returns does NOT include them yet (it is the ring
+ * position behind the batches that were answered).
+ * A BROKEN announcement -- a different next submission, or a launch set that does not match
+ * (dint_submit_segments_multi_ahead) -- fails with DINT_ESTATE and answers nothing; dint_snapshot and the state calls fail
+ * with DINT_ESTATE and leave the announcement pending.  After a broken announcement the engine is as if it had never seen the
+ * announced batch: tables, lock words and overflow pool (the first stage never touches them), the ring's tail and the count of
+ * records appended, dint_stats (bad_requests / foreign_requests the first stage counted are taken back; lock_fasst / lock_2pl:
+ * those two counters keep what the cancelled count stage added), and the drain cursor.  One thing stays: the ring slots from
+ * the tail onward hold the cancelled batch's log records, as many as it had log requests.  Nothing reads them as records, but
+ * a later tatp DELETE_LOG that lands on such a slot keeps the 40 val bytes it finds there (the reference's DELETE_LOG writes no
+ * val, tatp/udp/server_shard.cc:196-207), so it shows the cancelled batch's bytes where two plain calls would show older ones.
+ * Records drained between the two calls and then cancelled are the caller's to discard; the drain stream after the cancel goes
+ * on with the first record appended after it: nothing lost, nothing repeated, lost == 0.  (A cancelled batch that lapped the
+ * reader -- more records waiting to be drained plus its own than the ring holds -- has overwritten the oldest of them: the
+ * next drain reports those as lost, like any record the ring overwrote.)  The announced batch's reply buffer (= its request
+ * buffer, when in place) holds what the first stage wrote: undefined for the caller.
+ * dint_reset / dint_restore drop the announcement silently: the engine goes on as a fresh one / from the snapshot (ring, tail,
+ * drain cursor included).  lock_fasst / lock_2pl (batches of at most 65,536): the count
+ * stage of the next batch rides in this batch's resolve launch the same way (k_lock_pass); an engine with
+ * DINT_FLAG_INPUTS_READY takes an announcement only in a pass it does not pipe (kernel timing on) and ignores it otherwise.
+ * A dint_submit_device of more requests than one pass takes looks
  * ahead from pass to pass by itself (stream order already has the whole array complete). */
 int dint_submit_device_ahead(dint_engine_t *e, const void *d_reqs, uint32_t n, void *d_replies, const void *d_next_reqs,
                              uint32_t next_n, void *d_next_replies, void *stream);
@@ -269,7 +286,9 @@ int64_t dint_dump_rows(dint_engine_t *e, uint32_t table, uint64_t *keys, uint32_
  * Returns n (also when cap is smaller; only cap words are written). */
 int64_t dint_read_locks(dint_engine_t *e, uint32_t table, uint32_t *a, uint32_t *b, uint64_t cap);
 /* log ring: copies up to cap canonical 64-byte records
- * {u64 key; u8 val[40]; u32 ver; u8 is_del; u8 table; u8 pad[10]} and returns the tail index */
+ * {u64 key; u8 val[40]; u32 ver; u8 is_del; u8 table; u8 pad[10]} and returns the tail index: the ring position behind the
+ * batches answered so far (a batch announced by dint_submit_device_ahead has its records in the ring, from the tail on, but is
+ * not counted into the tail before it is submitted) */
 int64_t dint_read_log(dint_engine_t *e, void *records, uint64_t cap);
 /* Log drain (the reference writes its logs and never reads them, tatp/udp/server_shard.cc:182-207): copies
  * the records appended since the previous call, oldest first, up to cap; returns how many.  *lost (may be NULL) = records
@@ -282,7 +301,8 @@ int64_t dint_log_drain(dint_engine_t *e, void *records, uint64_t cap, uint64_t *
  * (ring wrap, reset / restore) -- the two calls may be mixed.  The copy runs on `stream` (a hipStream_t, NULL = the engine's
  * own) and is complete when the call returns: like dint_log_drain it synchronises the device to learn the tail; the 16 bytes of
  * the tail words are all that reaches host memory.  As for dint_log_drain, a batch announced by dint_submit_device_ahead has
- * its records in the ring already: they are drained with the rest. */
+ * its records in the ring already: they are drained with the rest (and are the caller's to discard should the announcement be
+ * broken: the cursor then goes back behind the last answered batch's records). */
 int64_t dint_log_drain_device(dint_engine_t *e, void *d_records, uint64_t cap, uint64_t *lost, void *stream);
 
 typedef struct dint_apply_stats {
@@ -775,8 +795,10 @@ int dint_submit_segments_multi(const dint_segments_item *items, uint32_t n_items
  * the one-launch pass): plain dint_submit_segments_multi.  The announced step MUST be the engines' next submission: it is
  * answered by all of the engines or by none.  Anything else submitted to one of them in between fails with DINT_ESTATE as
  * after dint_submit_device_ahead and cancels the announcement of EVERY engine of the set (the others drop theirs when they
- * are next called); the announced buffers then hold what the first stage wrote (log requests answered in place) and the
- * step is handed over again with its requests. */
+ * are next called); every engine of the set is then as if it had never seen the announced step (dint_submit_device_ahead: tail,
+ * appended count, dint_stats, drain cursor; the ring slots from the tail on keep the step's records).  The announced buffers
+ * hold what the first stage wrote (log requests answered in place): the step, if it is still wanted, is handed over again with
+ * its requests. */
 int dint_submit_segments_multi_ahead(const dint_segments_item *items, uint32_t n_items, const dint_segments_item *next, void *stream);
 /* d_home[i] = home shard (0..shard_count-1) of d_reqs[i], computed on the GPU with the
  * same hash/modulus the engine uses; 0xFF for requests that have no home (bad table). */

@@ -180,6 +180,16 @@ int dint_lock_gclient_get_stats(dint_lock_gclient_t *c, dint_fasst_client_stats 
  * choose (COMMIT_BCK 13 / INSERT_BCK 19 / DELETE_BCK 23).  No device call. */
 int dint_log_classify_host(const void *records, uint64_t n, const uint8_t *exists0, uint8_t *types_out);
 
+/* ---- log ring: tail words, appended count and drain cursor on the host (dint_amd/csrc/log_ring.h) ----------------
+ * What the partition stage of a pass, a kept or cancelled announcement (dint_submit_device_ahead) and dint_log_drain do to the
+ * ring of a tatp / smallbank engine of `cap` entries, walked over a script with the functions the engine and the kernels call.
+ * ops = n_ops pairs {code, arg}: 0 a plain pass of arg log records; 1 the running pass announces a batch of arg log records;
+ * 2 the announced batch is submitted; 3 the announcement is cancelled; 4 a drain into room for arg records.  The ring holds
+ * record ids 1, 2, 3 .. in append order (cancelled records included).  After every op four words go to out: {the tail
+ * dint_read_log returns, records appended, drain cursor, the other tail word}; a drain adds {n, lost, the n ids}.  Returns the
+ * words written; DINT_EINVAL: cap == 0, a null array, arg > cap, an op out of turn, more than out_cap words.  No device call. */
+int64_t dint_log_ring_host(uint32_t cap, const uint32_t *ops, uint32_t n_ops, uint64_t *out, uint64_t out_cap);
+
 /* ---- log fold: the rule on the host (dint_amd/csrc/log_fold.h) ---------------------------------------------------
  * What dint_log_apply_folded_device (include/dint_abi.h) decides for ONE chunk, restated over dumped rows for tests and tools:
  * workload = DINT_WL_TATP / DINT_WL_SMALLBANK with n_tables tables of hash_size[t] buckets (dint_hash_size); the replica's rows as

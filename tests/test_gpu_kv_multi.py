@@ -270,8 +270,8 @@ def _resume(m, what, fresh=None):
 
 @pytest.mark.parametrize("name", ["tatp3", "store3"])
 def test_a_set_with_other_buffers_than_the_announced_ones_is_refused(name, monkeypatch):
-    """tatp3 has a log: the cancelled partition appended step 4's records -- ahead_cancel rewinds the tail and the appended count,
-    so that log_drain counts them once"""
+    """tatp3 has a log: the cancelled partition appended step 4's records -- ahead_cancel takes them back (tail, appended count,
+    drain cursor), so that log_drain counts them once"""
     m = _Set(name, {}, monkeypatch)
     m.run(0, 4, True)
     other = m.upload(4)
@@ -281,6 +281,66 @@ def test_a_set_with_other_buffers_than_the_announced_ones_is_refused(name, monke
     for d, (a, _) in zip(other, m.host[4]):
         assert d.cpu().numpy().tobytes() == a.tobytes()  # (the refused call answered nothing)
     _one_set(_resume(m, "other buffers", other))
+
+
+def test_a_different_step_after_a_refused_set_leaves_no_trace_of_the_announced_one(monkeypatch):
+    """_resume hands the cancelled step over again, so the same records land on the same ring slots and nothing the cancel left
+    behind can show.  Here step 3 announces a step B of batches of its own (engine 1 idle in it; bad table ids in the others), a
+    step X of other batches is handed over instead -- refused --, then X again announcing Y, then Y.  Per engine the model of
+    tests/test_gpu_ahead_cancel.py: the oracle replays what was answered, B's records stay in the ring slots from the tail on
+    (X's and Y's DELETE_LOG records keep their val bytes), and nothing else of B: tail, drain, bad_requests (the line that fails
+    when the cancel does not take back what B's partition counted: 5 instead of 3 on engines 0 and 2)"""
+    import torch
+
+    import tracegen
+    from test_gpu_ahead_cancel import _Model, _spoil
+
+    m = _Set("tatp3", {}, monkeypatch)
+    s = m.s
+    sizes = {"b": (900, 0, 400), "x": (500, 800, 300), "y": (300, 200, 600)}
+    host, want, models = {k: [] for k in sizes}, {k: [] for k in sizes}, []
+    seg = lambda a: km._segmented(a, km.cuts_of(len(a)), s.seg_cap)[0]  # noqa: E731
+    for k, c in enumerate(s.cases):
+        mk = _Model(c.wl, c.log_cap, c.populate, c.engine["n_rows"])
+        for j in range(4):
+            if s.steps[j][k] is not None:
+                mk.answer(c.passes[s.steps[j][k]])
+        ex = mk.existing()
+        nb, nx, ny = (sizes[q][k] for q in "bxy")
+        b = _spoil(tracegen.tatp_random(nb, ex, seed=200 + k, n_sub_touch=40), [1, nb // 2] if nb else [])
+        tr = tracegen.tatp_random(nx + ny, ex, seed=210 + k, n_sub_touch=40)
+        x, y = _spoil(tr[:nx].copy(), [0, 100, 250], only=wire.Tatp.READ), tr[nx:].copy()
+        e0 = mk.o.errors
+        mk.cancel(b)
+        wx, wy = mk.answer(x), mk.answer(y)
+        assert mk.o.errors >= e0 + 3 and (nb == 0 or mk.shown >= 8), (k, mk.shown)
+        for q, a, w in (("b", b, b), ("x", x, wx), ("y", y, wy)):
+            host[q].append(seg(a))
+            want[q].append(seg(w))
+        models.append(mk)
+    dev = {q: [torch.from_numpy(a.copy()).cuda() for a in host[q]] for q in sizes}
+    torch.cuda.synchronize()
+    m.run(0, 3, True)
+    m.submit(3, ahead=dev["b"])
+    with pytest.raises(_lib.DintError, match="announced"):
+        m.submit(0, row=dev["x"])
+    m.st.synchronize()
+    for d, a in zip(dev["x"], host["x"]):
+        assert d.cpu().numpy().tobytes() == a.tobytes()  # (the refused call answered nothing)
+    m.submit(0, ahead=dev["y"], row=dev["x"])
+    m.submit(0, row=dev["y"])
+    m.st.synchronize()
+    m.check_replies(dev=m.dev[:4], what="a different step")
+    for k, (eng, mk, c) in enumerate(zip(m.engs, models, s.cases)):
+        for q in "xy":
+            assert dev[q][k].cpu().numpy().tobytes() == want[q][k].tobytes(), (q, k)
+        mk.check(eng)
+        assert eng.stats()["bad_requests"] == 3, (k, eng.stats()["bad_requests"])  # X's, once; B's two not at all
+        rec, lost = eng.log_drain(c.log_cap)
+        assert lost == 0 and len(rec) == len(mk.drained()), (k, len(rec), lost, len(mk.drained()))
+        assert (np.frombuffer(rec.tobytes(), "u1").reshape(-1, 64) == mk.drained()).all(), k
+    m.quiet()
+    _one_set(m.alone())
 
 
 def test_a_per_engine_call_between_a_set_and_its_announced_step_is_refused(monkeypatch):

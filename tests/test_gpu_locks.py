@@ -272,6 +272,51 @@ def test_inputs_ready_passes_overlap_and_match_the_oracle(wl):
             eng.restore()
 
 
+@pytest.mark.parametrize("toggle", [True, False], ids=["timing-toggled", "timing-off"])
+@pytest.mark.parametrize("wl", ["fasst", "tpl"])
+def test_inputs_ready_engine_answers_an_announced_batch_once(wl, toggle):
+    """DINT_FLAG_INPUTS_READY and an announcement.  A pass with kernel timing on is not piped: it takes the announcement and counts
+    batch k + 1 into scratch set 1.  With timing off again batch k + 1 would go piped and be counted a second time -- after exactly
+    one earlier piped pass into that same set (twice as many records per bin: wrong replies, or k_lock_count's bounded wait for a
+    region that is never named).  It must be resolved from the set it was counted into, once.  Three more batches
+    take every set of the rotation again.  timing-off: the same calls with timing off all along -- the piped path ignores the
+    announcements.  Replies and final lock words are the oracle's."""
+    from dint_amd import _lib
+    n, nb = 10_000, 6
+    if wl == "fasst":
+        mk_req, W_, o = tracegen.fasst_random, wire.Workload.FASST, orc.FasstOracle(1 << 16)
+    else:
+        mk_req, W_, o = tracegen.tpl_random, wire.Workload.TPL, orc.TplOracle(1 << 16)
+    reqs = [mk_req(n, seed=300 + k, n_hot=3, p_hot=0.4) for k in range(nb)]
+    want = [o.replay(r) for r in reqs]
+    eng = _engine(W_, n_slots=1 << 16, flags=_lib.FLAG_INPUTS_READY)
+    d = [torch.from_numpy(np.frombuffer(r.tobytes(), np.uint8).copy()).cuda() for r in reqs]
+    torch.cuda.synchronize()
+    ahead = lambda k: (d[k + 1], n, None) if k + 1 < nb else None  # noqa: E731
+    eng.submit_device(d[0], n, None, 0, ahead=None if toggle else ahead(0))  # one piped pass
+    if toggle:
+        eng.timing_enable(True)
+    eng.submit_device(d[1], n, None, 0, ahead=ahead(1))
+    if toggle:  # the announcement was taken (a snapshot is refused while one is pending, and leaves it pending) ...
+        with pytest.raises(_lib.DintError, match="pending"):
+            eng.snapshot()
+        eng.timing_enable(False)
+    else:  # ... and ignored by a piped pass
+        eng.snapshot()
+    eng.submit_device(d[2], n, None, 0, ahead=None if toggle else ahead(2))  # the announced batch
+    for k in range(3, nb):
+        eng.submit_device(d[k], n, None, 0, ahead=None if toggle else ahead(k))
+    eng.sync()
+    for k in range(nb):
+        assert d[k].cpu().numpy().tobytes() == want[k].tobytes(), k
+    a, b = eng.read_locks()
+    if wl == "fasst":
+        assert (a == o.locks).all() and (b == o.vers).all()
+    else:
+        assert (a == o.num_ex).all() and (b == o.num_sh).all()
+    assert eng.stats()["batches"] == nb
+
+
 @pytest.mark.parametrize("wl", ["fasst", "tpl"])
 def test_direct_big_bins_and_the_overflow_list_agree(wl, monkeypatch):
     """a pass of <= 65,536 requests stores a big bin's records beyond the 64 in place straight into a region of its own (two

@@ -83,7 +83,7 @@ T = wire.Tatp
 
 
 def tatp_random(n, existing, seed=0, n_sub_touch=40, well_formed=True, pools=None):
-    """Random mix of all 13 tatp request types.
+    """Random mix of the 11 tatp request types the reference servers handle (no COMMIT, no malformed type).
 
     `existing` = list of 5 key arrays (rows that exist initially, e.g. from the
     oracle's populate dump restricted to s_id < n_sub_touch).  With

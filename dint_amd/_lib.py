@@ -37,8 +37,11 @@ SYMBOLS = [
     "dint_load_rows_device", "dint_populate_device",
     "dint_state_verify", "dint_state_compact",
     "dint_state_block_digest", "dint_state_block_select", "dint_state_block_rows", "dint_state_block_diff",
-    "dint_records_route",
+    "dint_records_route", "dint_traffic_report",
 ]
+#: dint_traffic_report: requests / list entries a call takes at most
+TRAFFIC_MAX_N = 1 << 24
+TRAFFIC_MAX_TOP = 4096
 #: dint_log_apply_folded_device flags
 FOLD_DRY_RUN = 1
 #: dint_state_rehash flags
@@ -161,6 +164,33 @@ class TableStats(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: (list(getattr(self, k)) if k.endswith("_hist") else int(getattr(self, k))) for k, _ in self._fields_ if k != "reserved"}
+
+
+class TrafficKey(C.Structure):
+    """dint_traffic_key (include/dint_abi.h)"""
+    _fields_ = [("key", C.c_uint64)] + [(k, C.c_uint32) for k in (
+        "table", "requests", "reads", "locks", "unlocks", "writes", "rejects", "misses", "first_index", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class TrafficReport(C.Structure):
+    """struct dint_traffic_report (include/dint_abi.h)"""
+    _fields_ = [(k, C.c_uint64) for k in (
+        "n", "keyed", "bad_table", "log_requests", "reads", "locks", "unlocks", "writes", "others", "rejects", "misses",
+        "distinct_keys", "distinct_units", "distinct_lock_slots", "max_key_requests", "max_unit_requests", "max_unit", "max_unit_table",
+        "shared_units", "shared_unit_requests", "shared_unit_rejects", "shared_slots", "shared_slot_requests", "shared_slot_rejects",
+        "n_by_requests", "n_by_rejects", "temp_bytes")] + [
+        ("reserved", C.c_uint64 * 5), ("key_hist", C.c_uint64 * 25), ("unit_hist", C.c_uint64 * 25),
+        ("req_types", (C.c_uint64 * 32) * 5), ("rep_types", (C.c_uint64 * 32) * 5)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ("reserved", "key_hist", "unit_hist", "req_types", "rep_types")}
+        d["key_hist"], d["unit_hist"] = list(self.key_hist), list(self.unit_hist)
+        d["req_types"] = [list(r) for r in self.req_types]
+        d["rep_types"] = [list(r) for r in self.rep_types]
+        return d
 
 
 class TableVerify(C.Structure):
@@ -316,6 +346,9 @@ def load() -> C.CDLL:
         # ... and the record routing's rule (csrc/state_route.h) over a list in host memory
         "dint_records_route_host": (i64, [u32, u64, u32, vp, u64, vp, vp]),
         "dint_records_route_tile": (u32, []),
+        # the traffic report (csrc/traffic_report.h): a batch in device memory / the same rule over a batch in host memory
+        "dint_traffic_report": (C.c_int, [vp, vp, vp, u64, u32, C.POINTER(TrafficReport), vp, vp, vp]),
+        "dint_traffic_report_host": (C.c_int, [u32, u64, u64, u32, vp, vp, u64, u32, C.POINTER(TrafficReport), vp, vp]),
         # ... and the rehash's layout rule (csrc/state_rehash.h) over keys in source order
         "dint_state_rehash_place_host": (i64, [vp, u64, u64, u32, u32, vp, vp, vp]),
         # ... and the bulk load's rule (csrc/state_load.h): placement over a host view, the population's rows, its tile tables

@@ -24,6 +24,7 @@
 #include "state_load.h"
 #include "state_rehash.h"
 #include "state_stats.h"
+#include "dint_traffic.h"
 
 // k_locks.hip: one half of a lock pass (stage 1 = count + scan / place, 2 = resolve) on `st`
 void dint_launch_lock_stage(uint32_t workload, int stage, const void *d_req, void *d_rep, uint32_t n, uint2 *table, dint_mod slots,
@@ -2032,6 +2033,32 @@ int64_t dint_state_diff(dint_engine_t *a, dint_engine_t *b, void *d_records, uin
     out->total = h[4]; out->only_a = h[0]; out->only_b = h[1]; out->val_differs = h[2]; out->ver_only = h[3];
   }
   return (int64_t)std::min<uint64_t>(h[4], d_records ? cap : 0);
+}
+
+// ---- traffic report (k_traffic.hip; traffic_report.h) ---------------------------------------------------------------------------
+int dint_traffic_report(dint_engine_t *e, const void *d_reqs, const void *d_replies, uint64_t n, uint32_t top_k, struct dint_traffic_report *out,
+                        dint_traffic_key *by_requests, dint_traffic_key *by_rejects, void *stream) {
+  if (!e || !out) return fail(DINT_EINVAL, "null argument");
+  if (e->cfg.workload == DINT_WL_LOG) return fail(DINT_ESTATE, "a log_server batch has no keys to report");
+  if (n > DINT_TRAFFIC_MAX_N) return fail(DINT_EINVAL, "%llu requests: a report takes 2^24 at most", (unsigned long long)n);
+  if (top_k > DINT_TRAFFIC_MAX_TOP) return fail(DINT_EINVAL, "top_k %u: %u at most", top_k, DINT_TRAFFIC_MAX_TOP);
+  if (top_k && (!by_requests || !by_rejects)) return fail(DINT_EINVAL, "top_k entries need both lists");
+  if (n && !d_reqs) return fail(DINT_EINVAL, "n requests need a request array");
+  if (n && d_replies == d_reqs) return fail(DINT_EINVAL, "an in-place reply array has lost the requests' types: hand over the pristine requests");
+  tr_geom g;
+  if (!dint_traffic_geom(e->cfg.workload, e->cfg.n_slots, e->cfg.n_rows, e->cfg.flags, &g)) return fail(DINT_ESTATE, "workload keeps no keys");
+  // (tables, pass scratch and an announced batch are not touched: no quiet engine is asked for; the lock orders the call among the
+  // engine's other calls on its streams)
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  dint_traffic_scratch s;  // the call's own temporary memory: allocated by it, freed before it returns -- the engine holds none of it
+  const int rc = dint_traffic_run(g, s, d_reqs, d_replies, n, top_k, st, out, by_requests, by_rejects);
+  if (rc) (void)hipStreamSynchronize(st);  // (a failed call may have left work queued that reads the scratch)
+  dint_traffic_free(s);
+  if (int rc2 = mark_stream(e, st)) return rc2;
+  return rc;
 }
 
 // ---- record routing (k_rroute.hip; state_route.h) -------------------------------------------------------------------------------

@@ -453,6 +453,22 @@ class Engine:
         n = _lib.check(rc)
         return self.last_compact[:n]
 
+    # ---- traffic report (dint_traffic_report) ----------------------------------------------------------------
+    def traffic_report(self, d_reqs, n: int, d_replies=None, top: int = 16, stream: int = 0) -> dict:
+        """dint_traffic_report: one batch of n wire messages in HBM (and, d_replies given, the replies it got -- a buffer of
+        its own: an in-place reply has lost the request types) as a dict of the fields of struct dint_traffic_report
+        (include/dint_abi.h; csrc/traffic_report.h is the rule): counts by class and reply flag, distinct keys / units / lock
+        slots, key_hist, unit_hist, req_types and rep_types as lists, the shared_* numbers, and "by_requests" / "by_rejects":
+        lists of at most `top` dicts of dint_traffic_key.  Read-only; leaves a batch announced with submit_device(ahead=)
+        pending.  dint_amd.traffic formats and merges these dicts."""
+        from .traffic import unpack
+
+        out = _lib.TrafficReport()
+        a, b = (_lib.TrafficKey * max(top, 1))(), (_lib.TrafficKey * max(top, 1))()
+        _lib.check(self._L.dint_traffic_report(self._h, _ptr(d_reqs) if d_reqs is not None else None, None if d_replies is None else _ptr(d_replies),
+                                               n, top, C.byref(out), a, b, stream))
+        return unpack(out, a, b)
+
     def stats(self) -> dict:
         s = _lib.Stats()
         _lib.check(self._L.dint_get_stats(self._h, C.byref(s)))

@@ -722,6 +722,66 @@ typedef struct dint_table_compact {
  * compaction restores the engine as it was before it.  No content of the tables makes the kernels read or write outside them
  * and the staging buffer or loop without bound.  The caller keeps the engine quiet meanwhile. */
 int dint_state_compact(dint_engine_t *e, dint_table_compact *out, uint32_t cap_tables, uint32_t flags, void *stream);
+/* ---- traffic report (v5, additive): a batch's hot keys, reply codes and shared lock slots -- read where the batch lies ----------
+ * The tables have dint_state_stats; this is the same for the REQUEST STREAM: what one batch of wire messages (and, optionally, the
+ * replies it got) looks like in the terms DESIGN.md 3 decides a pass's speed by -- requests per key and per unit of serial order,
+ * keys that share a unit or a lock slot, REJECT / NOT_EXIST replies.  dint_amd/csrc/traffic_report.h is the rule (decode, class of a
+ * request, flags of a reply, unit, lock slot); lock_fasst, lock_2pl, store, tatp and smallbank engines (log_server: DINT_ESTATE).
+ * Every number is exact and independent of scheduling.  All sizes are the GLOBAL ones of the engine's configuration: a shard
+ * reports what the unsharded engine reports over the same arrays. */
+typedef struct dint_traffic_key {
+  uint64_t key;          /* the key (lock tables: the lid) */
+  uint32_t table;
+  uint32_t requests;     /* keyed requests on (table, key): = reads + locks + unlocks + writes + the OTHER class */
+  uint32_t reads, locks, unlocks, writes;
+  uint32_t rejects, misses; /* replies flagged REJECT / MISS (0 without a reply array) */
+  uint32_t first_index;  /* the lowest request index of the key */
+  uint32_t reserved;     /* 0 */
+} dint_traffic_key;
+struct dint_traffic_report { /* (a struct tag only: the call below has the name) */
+  uint64_t n;            /* requests of the batch */
+  uint64_t keyed;        /* requests with a table the workload has that are no LOG request: what everything per key is over */
+  uint64_t bad_table;    /* requests whose table byte names a table the workload has not: counted here and nowhere else */
+  uint64_t log_requests; /* tatp COMMIT_LOG / DELETE_LOG, smallbank COMMIT_LOG: in the type histograms and here only */
+  uint64_t reads, locks, unlocks, writes, others; /* the keyed requests by class */
+  uint64_t rejects, misses;                       /* replies of keyed requests flagged REJECT / MISS */
+  uint64_t distinct_keys;       /* distinct (table, key) among the keyed requests */
+  uint64_t distinct_units;      /* distinct units: lock tables the lock slot, kv the (table, bucket) */
+  uint64_t distinct_lock_slots; /* tatp / smallbank: distinct (table, lock slot) the LOCK / UNLOCK / WRITE-PRIM requests touch; else 0 */
+  uint64_t max_key_requests, max_unit_requests;
+  uint64_t max_unit, max_unit_table; /* the unit that attains max_unit_requests: the lowest table, then the lowest unit id (n == 0: 0, 0) */
+  uint64_t shared_units;         /* units that at least 2 distinct keys of the batch touch */
+  uint64_t shared_unit_requests; /* keyed requests on them */
+  uint64_t shared_unit_rejects;  /* REJECT replies on them */
+  uint64_t shared_slots;         /* tatp / smallbank: lock slots that LOCK / UNLOCK / WRITE-PRIM requests of at least 2 distinct keys touch */
+  uint64_t shared_slot_requests; /* ... those requests on them */
+  uint64_t shared_slot_rejects;  /* ... their REJECT replies */
+  uint64_t n_by_requests, n_by_rejects; /* entries written to the two lists */
+  uint64_t temp_bytes;           /* temporary device memory the call allocated and freed; host form: 0 */
+  uint64_t reserved[5];
+  uint64_t key_hist[25];         /* bin b: distinct keys with 2^b <= requests < 2^(b+1) */
+  uint64_t unit_hist[25];        /* ... distinct units */
+  uint64_t req_types[5][32];     /* per table: requests by type byte, bin 31 = every byte >= 31 (LOG requests included) */
+  uint64_t rep_types[5][32];     /* ... replies by type byte, under the REQUEST's table (all 0 without a reply array) */
+};
+#define DINT_TRAFFIC_MAX_N (1ull << 24)
+#define DINT_TRAFFIC_MAX_TOP 4096u
+/* (v5, additive) the report of the n wire messages at d_reqs (DEVICE memory, any alignment) and -- d_replies != NULL -- of the
+ * replies they got, replies[i] answering reqs[i] (any alignment; NULL: every reply-derived field is 0 and the by-rejects list
+ * empty).  by_requests / by_rejects: HOST arrays of top_k entries (top_k <= 4096; 0: no lists, the pointers may be NULL) that take
+ * the keys with the most requests / the most REJECT replies (only keys with at least one), ordered by that count descending, then
+ * table ascending, then key ascending -- the order and the cut are deterministic.  Read-only: the call reads the two arrays and the
+ * engine's geometry; it writes no table, no pass scratch and no dint_stats, needs no quiet engine, and leaves a batch announced by
+ * dint_submit_device_ahead pending.  It runs on `stream` (a hipStream_t, NULL = the engine's own), ordered behind what that
+ * stream holds and behind the engine's pending work, and is a diagnostic BESIDE the passes: it synchronises the stream THREE
+ * times (the keyed count, the distinct keys, the result) and returns with everything on the host.  Temporary device memory of
+ * about 160 bytes per request is the call's own: allocated by the call and freed before it returns (the free waits for the device
+ * to be idle); the engine object holds none of it, and nothing of the engine's own memory or of its other calls changes.
+ * Refused with nothing written to out or the lists: a null engine / d_reqs with n > 0 / out, lists missing with top_k > 0,
+ * top_k > 4096, n > 2^24, d_replies == d_reqs -- an in-place reply has lost the request's type: keep the pristine copy --
+ * (DINT_EINVAL); a log_server engine (DINT_ESTATE). */
+int dint_traffic_report(dint_engine_t *e, const void *d_reqs, const void *d_replies, uint64_t n, uint32_t top_k,
+                        struct dint_traffic_report *out, dint_traffic_key *by_requests, dint_traffic_key *by_rejects, void *stream);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

@@ -338,6 +338,19 @@ int64_t dint_records_route_host(uint32_t workload, uint64_t n_rows, uint32_t dst
 /* records per workgroup of dint_records_route's kernels: the sizes at which the device path changes shape (one tile, two, ...) */
 uint32_t dint_records_route_tile(void);
 
+/* ---- traffic report: the rule over caller-provided memory (dint_amd/csrc/traffic_report.h) -------------------------------------
+ * dint_traffic_report (include/dint_abi.h) over a batch in HOST memory, at any alignment: reqs / replies (may be NULL) = n wire
+ * messages of `workload`; the geometry is that of an engine created with (workload, n_slots, n_rows, flags) -- lock tables n_slots
+ * (0: the reference's 36,000,000), kv workloads the bucket counts dint_engine_create derives from n_rows, through the function it
+ * derives them with (no dint_config flag changes a bucket count today; `flags` is handed to that function so that one that does is
+ * followed here too).  out, the two lists (top_k entries each), their order and every refusal are the device call's; temp_bytes
+ * is 0.  A refused call writes nothing.  No device call. */
+struct dint_traffic_report; /* include/dint_abi.h */
+struct dint_traffic_key;
+int dint_traffic_report_host(uint32_t workload, uint64_t n_slots, uint64_t n_rows, uint32_t flags, const void *reqs, const void *replies,
+                             uint64_t n, uint32_t top_k, struct dint_traffic_report *out, struct dint_traffic_key *by_requests,
+                             struct dint_traffic_key *by_rejects);
+
 #ifdef __cplusplus
 }
 #endif

@@ -243,6 +243,33 @@ def keys_like(key: int, hash_size: int, n: int, *, same_kh: bool, same_quadrant:
     raise AssertionError("no such keys among 2^32 candidates")
 
 
+def keys_in_cells(hash_size: int, cells, per: int, seed: int, key_of=None, exclude=()) -> np.ndarray:
+    """(len(cells), per) distinct keys, row c in cell cells[c] = (global bucket, lock quadrant) of hash_size, none of `exclude`:
+    the keys of the shard-aware layout "edge" (tests/opwords.py), whose places are chosen by bucket and quadrant"""
+    cells = np.asarray(cells, np.int64).reshape(-1, 2)
+    want = cells[:, 1] * hash_size + cells[:, 0]  # = the lock word
+    assert len(np.unique(want)) == len(want)
+    rng = np.random.default_rng(seed)
+    out = np.zeros((len(cells), per), np.uint64)
+    have = np.zeros(len(cells), np.int64)
+    order = np.argsort(want)
+    for _ in range(64):
+        cand = rng.integers(1 << 33, 1 << 48, 1 << 20, dtype=np.uint64)
+        cand = np.unique(key_of(cand) if key_of else cand)
+        cand = cand[~np.isin(cand, np.asarray(exclude, np.uint64)) & ~np.isin(cand, out)]
+        b, q, _ = key_sig(cand, hash_size)
+        lw = (q * np.uint64(hash_size) + b).astype(np.int64)
+        at = np.searchsorted(want[order], lw)
+        hit = np.nonzero(want[order][np.minimum(at, len(want) - 1)] == lw)[0]
+        for k, c in zip(cand[hit], order[at[hit]]):
+            if have[c] < per:
+                out[c, have[c]] = k
+                have[c] += 1
+        if (have == per).all():
+            return out
+    raise AssertionError("not enough candidate keys for every cell")
+
+
 def collision_groups(hash_size: int, n_groups: int, per_group: int, seed: int, key_of=None) -> np.ndarray:
     """(n_groups, per_group) distinct keys: a row shares bucket and key-hash bits, different rows lie in different buckets.
     A birthday search over the cells (bucket, key hash) of 200,000 candidates, doubled until there are enough."""

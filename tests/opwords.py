@@ -7,7 +7,8 @@ from (lock free or held, counters 0 / 1 / 2, row present / absent / held twice).
 cold   every (start, word) with 1 <= len(word) <= Lc on a slot or key of its own: one submit of all preambles, then the words
        adjacent (word after word) or transposed (op 0 of every word, then op 1 of every word ...).  Layouts: "spread" (own lock
        words), "lockpair" (tatp / smallbank: two words on two keys of one bucket AND lock quadrant), "alias" / "line" (locks: two
-       words on two lids of one slot / on neighbouring slots of one 128-byte line).
+       words on two lids of one slot / on neighbouring slots of one 128-byte line).  For sets of H sharded engines
+       (tests/shardsplit.py) two more, placed by the shard geometry: "edge" (cold_edge) and "localline" (cold_localline).
 hot    every (start, word) with len(word) == Lh on ONE slot or row, block after block: preamble(start) + word + cleanup.  The
        trace is built against a live oracle: after the word the oracle's state of the slot is read and the ops that lead back to
        idle are emitted (releases, ABORT, INSERT / DELETE until the row is what the next start wants); the oracle's replies along
@@ -423,6 +424,8 @@ class Cold:
     adjacent: np.ndarray = None
     transposed: np.ndarray = None
     block_of: dict = field(default_factory=dict)  # arrangement -> the word of every request
+    tables: np.ndarray = None    # layout "edge": the table of every word (the other layouts: the target's tables)
+    pairs: list = None           # the shard-aware layouts: (kind, shard, word a, word b) of every pair that shares what `kind` says
 
     def final_states(self):
         """the oracle's state of every word's slot after preamble + word (layout "spread": every word from its true start)"""
@@ -477,6 +480,135 @@ def cold(name, target, layout="spread") -> Cold:
     c.transposed, c.block_of["transposed"] = build(lambda i: blocks[i][1], True, 32)
     assert len(c.adjacent) <= COLD_MAX
     return c
+
+
+# ---- cold, placed by the geometry of a set of H shards ---------------------------------------------------------------------------------
+# Shard g % H is home to global bucket / slot g and holds it at local index g // H; every shard's tables have n_local = ceil(size / H)
+# local buckets, kv group keys are gk_base[t] + local with gk_base summed from the n_local values, kv lock words sit at
+# q * n_local + local.  "edge" (kv) and "localline" (locks) put words where that arithmetic has its edges.
+def _arranged(c: Cold, pre_of, tabs_of):
+    """fill c.pre / adjacent / transposed as cold() does, word i on the tables tabs_of(i) (all of one length)"""
+    spec, keys, blocks = c.spec, c.keys, c.blocks
+
+    def build(ops_of, transposed, seed):
+        rows = [(k, i, op) for i in range(len(blocks)) for k, op in enumerate(ops_of(i))]
+        if transposed:
+            rows.sort(key=lambda r: r[0])
+        rep = len(tabs_of(0))
+        idx = np.repeat(np.array([r[1] for r in rows], np.int64), rep)
+        codes = np.repeat(np.array([r[2] for r in rows], np.int64), rep)
+        tabs = np.array([tabs_of(r[1]) for r in rows], np.int64).ravel()
+        return requests(spec, codes, tabs, keys[idx], seed), idx
+
+    c.pre, c.block_of["pre"] = build(pre_of, False, 41)
+    c.adjacent, c.block_of["adjacent"] = build(lambda i: blocks[i][1], False, 42)
+    c.transposed, c.block_of["transposed"] = build(lambda i: blocks[i][1], True, 42)
+    return c
+
+
+def kv_hash_sizes(spec, big=False):
+    if spec.wl == W.STORE:
+        return [sizes(spec, big)[0] * 18 // 4]
+    o = oracle(spec, big)
+    return [int(o.hash_size(t)) for t in range(5 if spec.wl == W.TATP else 2)]
+
+
+def edge_places(hash_sizes, H):
+    """(table, shard) of every shard whose TOP local bucket n_local - 1 of the table corresponds to a global bucket (the greatest
+    the shard is home to): there group key gk_base[t] + n_local - 1 is followed by gk_base[t + 1] + 0, the shard's local bucket 0
+    (global bucket = shard index) of the next table"""
+    return [(t, i) for t, hs in enumerate(hash_sizes) for i in range(H) if -(-hs // H) >= 2 and (-(-hs // H) - 1) * H + i < hs]
+
+
+EDGE_PER = 4  # keys per (bucket, lock quadrant) of a top bucket: 16 rows in that bucket at the most
+
+
+@functools.lru_cache(None)
+def cold_edge(name, H) -> Cold:
+    """layout "edge": pairs of words, for every place (t, i) of edge_places and every lock quadrant q, on
+      cross     a key of shard i's top bucket of table t, quadrant q | a key of global bucket i of table t + 1 (the shard's local
+                bucket 0 there), quadrant q: neighbours in group-key space, so a coarse bin can hold the end of one table and the
+                start of the next;
+      wrap      the last table (store: the only one): the top bucket | the least local bucket of the same table;
+      quadrant  a second key of the top bucket, quadrant q | a key of local bucket 0 of table t, quadrant q + 1: for q = 0..2 their
+                lock words q * n_local + n_local - 1 and (q + 1) * n_local are neighbours (q = 3 pairs with quadrant 0).
+    The keys are searched, not populated (tables of the small size, where H = 2 and H = 8 leave remainders in every table): a
+    word's preamble INSERTs its row where the start wants one; smallbank's rows cannot be inserted, so its words start from the
+    `absent` starts alone.  There are as many words as places: all of length 1 and an evenly spaced sample of the longer ones."""
+    spec = SPECS[name]
+    hs = kv_hash_sizes(spec)
+    places = edge_places(hs, H)
+    o = oracle(spec) if spec.wl != W.STORE else None
+    top = lambda t, i: (-(-hs[t] // H) - 1) * H + i  # noqa: E731
+    T, B = {}, {}
+    for t in range(len(hs)):
+        taken = np.zeros(0, np.uint64) if o is None else o.dump(t)[0]
+        mine = [i for tt, i in places if tt == t]
+        below = sorted({i for tt, i in places if tt in (t, t - 1)})  # local bucket 0: the partner of table t's and of table t - 1's tops
+        cells = [(top(t, i), q) for i in mine for q in range(4)] + [(i, q) for i in below for q in range(4)]
+        if not cells:
+            continue
+        k = kvkeys.keys_in_cells(hs[t], cells, 2 * EDGE_PER, 60 + t, exclude=taken)
+        for (b, q), row in zip(cells[:4 * len(mine)], k):
+            T[t, b % H, q] = row
+        for (b, q), row in zip(cells[4 * len(mine):], k[4 * len(mine):]):
+            B[t, b, q] = row
+    slots, pairs = [], []  # (table, key) of every word; the pairs
+    for t, i in places:
+        for q in range(4):
+            for k in range(EDGE_PER):
+                if k % 2:
+                    kind, other = "quadrant", (t, int(B[t, i, (q + 1) % 4][k]))
+                elif t + 1 < len(hs):
+                    kind, other = "cross", (t + 1, int(B[t + 1, i, q][k]))
+                else:
+                    kind, other = "wrap", (t, int(B[t, i, q][EDGE_PER + k]))
+                pairs.append((kind, i, len(slots), len(slots) + 1))
+                slots += [(t, int(T[t, i, q][k])), other]
+    n = len(slots)
+    starts = tuple(s for s in spec.starts if spec.wl != W.SMALLBANK or s.endswith("-absent"))
+    L = cold_length(spec, spec.targets[0])
+    one = [(s, w) for s in starts for w in words(spec, 1)]
+    more = [(s, w) for s in starts for k in range(2, L + 1) for w in words(spec, k)]
+    assert n > len(one), (n, len(one))
+    blocks = one + _spaced(more, n - len(one))
+    rng = np.random.default_rng(5)
+    blocks = [blocks[j] for j in rng.permutation(n)]  # (no op length or start tied to a kind of place)
+    c = Cold(spec, "edge", "edge", L, blocks, np.array([k for _, k in slots], np.uint64), tables=np.array([t for t, _ in slots]), pairs=pairs)
+    assert len(np.unique(c.keys)) == n
+    absent = (0,) if spec.wl == W.STORE else (0, 0)
+    pre = (lambda b: cold_preamble(spec, blocks[b][0])) if spec.wl == W.SMALLBANK else (lambda b: fix_ops(spec, absent, start_state(spec, blocks[b][0])))
+    return _arranged(c, pre, lambda b: (int(c.tables[b]),))
+
+
+def _localline_lids(n, H):
+    first, _ = _lid_maps()
+    per = -(-((n + 1) // 2) // H)
+    out = []
+    for i in range(H):  # global slots g and g + H of home i: locals l and l + 1, l even and both on one line of 16 slots
+        g = np.arange(i, N_SLOTS - H, H)
+        g = g[((g // H) % 2 == 0) & (first[g] != 0) & (first[g + H] != 0)]
+        last = i + (N_SLOTS - 1 - i) // H * H
+        g = _spaced(g[(g != i) & (g != last) & (g + H != last)], per)
+        assert first[last] and first[i], (i, last)
+        out.append(np.concatenate([[[first[last], first[i]]], np.stack([first[g], first[g + H]], axis=1)]))  # (the last local slot | local 0)
+    return np.stack(out, axis=1).reshape(-1, 2)  # pair k of shard 0, of shard 1 ... pair k + 1 of shard 0
+
+
+@functools.lru_cache(None)
+def cold_localline(name, H) -> Cold:
+    """layout "localline": every word of cold(), pairs of words on two lids of ONE home whose LOCAL slots are neighbours on one
+    128-byte line of that shard's table -- global slots g and g + H, which the unsharded engine holds H slots apart; the first pair
+    of every shard on the shard's last local slot and its local slot 0"""
+    spec = SPECS[name]
+    L = cold_length(spec, "slot")
+    blocks = [(s, w) for s in spec.starts for k in range(1, L + 1) for w in words(spec, k)]
+    lids = _localline_lids(len(blocks), H)
+    m = len(blocks) // 2
+    pairs = [("ends" if k < H else "line", k % H, 2 * k, 2 * k + 1) for k in range(m)]
+    c = Cold(spec, "slot", "localline", L, blocks, lids.ravel()[:len(blocks)].astype(np.uint32), pairs=pairs)
+    assert len(np.unique(c.keys)) == len(blocks)
+    return _arranged(c, lambda b: cold_preamble(spec, blocks[b][0]), lambda b: (0,))
 
 
 # ---- hot --------------------------------------------------------------------------------------------------------------------------
@@ -666,12 +798,17 @@ def dual_keys(name):
     return tuple(int(x) for x in _lock_pairs(np.arange(POP, dtype=np.uint64), hs)[0])
 
 
-def dual(name, target, ratio):
+def localline_dual_lids(H):
+    """two lids of one home of a set of H lock shards on neighbouring LOCAL slots of one 128-byte line: global slots g and g + H"""
+    return tuple(int(x) for x in _localline_lids(4 * H, H)[H])  # (the pairs in front are the shards' last slot | slot 0)
+
+
+def dual(name, target, ratio, keys=None):
     """the hot trace on one key and the same trace rotated by half its blocks on the other, interleaved ratio : 1.  The per-block
-    start states do not hold here; the expected replies are one oracle replay of the whole"""
+    start states do not hold here; the expected replies are one oracle replay of the whole.  keys: dual_keys(name) unless given"""
     spec = SPECS[name]
     h = hot(name, target)
-    ka, kb = dual_keys(name)
+    ka, kb = keys or dual_keys(name)
     cut = int(h.block_off[len(h.blocks) // 2])
     a, b = h.req.copy(), np.concatenate([h.req[cut:], h.req[:cut]])
     set_place(spec, a, a["table"] if "table" in a.dtype.names else 0, ka)

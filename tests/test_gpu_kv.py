@@ -315,6 +315,18 @@ def test_two_shards_on_one_gpu_equal_one_server(wl):
     wrong = shards[0].submit(req[home == 1][:100])
     assert wrong.tobytes() == req[home == 1][:100].tobytes()
     assert shards[0].stats()["foreign_requests"] == 100
+    # the state: every shard holds the projection of the one server's rows, lock words and counters (tests/shardsplit.py)
+    import shardsplit as ss
+
+    for i, s in enumerate(shards):
+        for t in range({"store": 1, "tatp": 5, "smallbank": 2}[wl]):
+            hs = 5000 * 18 // 4 if wl == "store" else o.hash_size(t)
+            assert _same_rows(s.dump_rows(t), ss.project_rows(o.dump() if wl == "store" else o.dump(t), hs, i, 2)), (i, t)
+            if wl == "tatp":
+                assert (s.read_locks(t)[0] == ss.project_kv_locks(o.locks(t), hs, i, 2)).all(), (i, t)
+            elif wl == "smallbank":
+                ex, sh = s.read_locks(t)
+                assert (ex == ss.project_kv_locks(o.num_ex(t), hs, i, 2)).all() and (sh == ss.project_kv_locks(o.num_sh(t), hs, i, 2)).all(), (i, t)
 
 
 # ---------------------------------------------------------------- closed-form vs request-by-request resolution

@@ -2418,7 +2418,7 @@ __device__ static inline uint32_t kv_piece_of(uint32_t idx, uint32_t np, uint32_
   return p < np ? p : np - 1;
 }
 // work items of k_kv_big (bigq): KVQ_W uint4 each
-//   [0] = {bin = coarse bin + C * sub, offset of the sub in ovf, records of the sub, kind | piece << 2 | pieces << 8}
+//   [0] = {bin = coarse bin + C * sub, offset of the sub in ovf, records of the sub, kind | piece << 2 | pieces << 10}
 //   [1] = kind 0: unused.  Else {hot key lo, hi, item index of the sub's first item, -}
 //   [2] = kind 0: unused.  Else {one record of the hot key (big path's form) lo, hi, -, -}
 #define KVQ_W 3u

@@ -100,7 +100,7 @@ def _cold_sel(rng, free, n_cold):
 
 # ---- tatp ---------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(None)
-def _tatp_base(n_sub=N_SUB):
+def tatp_base(n_sub=N_SUB):
     o = orc.TatpOracle(n_sub, log_entries=16)
     return [o.dump(t)[0].copy() for t in range(5)], [o.hash_size(t) for t in range(5)]
 
@@ -118,7 +118,7 @@ TATP_KEY_OF = (None, None, sf_key_of, sf_key_of, kvkeys.cf_key_of)
 def _tatp_pools(avoid):
     """tatp_random's own pools for every subscriber (the populated rows and the plausible missing ones), without the keys of the
     (table, bucket) pairs in `avoid`: noise that stays out of a hot row's bucket"""
-    existing, hs = _tatp_base()
+    existing, hs = tatp_base()
     s = np.arange(N_SUB, dtype=np.uint64)
     a = (np.arange(1, 5, dtype=np.uint64) << np.uint64(32))[None, :]
     sf = (s[:, None] | a).ravel()
@@ -134,14 +134,14 @@ def _tatp_pools(avoid):
     return tuple(pools)
 
 
-def _tatp_noise(n, seed, avoid):
-    existing, _ = _tatp_base()
+def tatp_noise(n, seed, avoid):
+    existing, _ = tatp_base()
     return tracegen.tatp_random(n, existing, seed=seed, pools=_tatp_pools(avoid))
 
 
 def tatp_insert_pass(rows, seed, avoid):
     """a first small pass that INSERTs the (table, key) rows in `rows`, so that the neighbours exist"""
-    req = _tatp_noise(200, seed, avoid)
+    req = tatp_noise(200, seed, avoid)
     for k, (tb, key) in enumerate(rows):
         at = 20 + 30 * k
         req["type"][at], req["table"][at], req["key"][at] = T.INSERT_PRIM, tb, key
@@ -149,7 +149,7 @@ def tatp_insert_pass(rows, seed, avoid):
 
 
 def tatp_bucket_of(table, key):
-    return (table, int(kvkeys.np_bucket(np.array([key], np.uint64), _tatp_base()[1][table])[0]))
+    return (table, int(kvkeys.np_bucket(np.array([key], np.uint64), tatp_base()[1][table])[0]))
 
 
 @functools.lru_cache(None)
@@ -158,7 +158,7 @@ def tatp_hot_pair(same_quadrant: bool, share: str, control: bool = False, hot: i
     in its lock quadrant or not; N is inserted by pass 0, requested in passes 1 .. 5 and absent from pass 6.  `share`: "cold" = 1 .. 8
     requests of N per pass (about 0.3 %), "warm" = 6 %, "equal" = 35 % each.  control: the same trace with N' instead of N, a key
     of the bucket with OTHER key-hash bits in another quadrant."""
-    hs = _tatp_base()[1][0]
+    hs = tatp_base()[1][0]
     n_key = int(kvkeys.keys_like(hot, hs, 1, same_kh=not control, same_quadrant=same_quadrant and not control, seed=11)[0])
     avoid = (tatp_bucket_of(0, hot),)
     rng = np.random.default_rng(5)
@@ -167,7 +167,7 @@ def tatp_hot_pair(same_quadrant: bool, share: str, control: bool = False, hot: i
     p_h = 0.35 if share == "equal" else 0.6
     hot_min = {}
     for k, n in enumerate(HOT_PASSES):
-        req = _tatp_noise(n, 17 * k + 5, avoid)
+        req = tatp_noise(n, 17 * k + 5, avoid)
         u = rng.random(n)
         h_sel = u < p_h
         _overlay(req, rng, 0, hot, h_sel, *TATP_SIMPLE)
@@ -189,7 +189,7 @@ def tatp_cf_pair(p_hot: float, n_writes: bool) -> Case:
     """case c: the hot CALL_FORWARDING row (4, 7 | 1 << 32) inserted and deleted by its own requests, beside a well-formed
     CALL_FORWARDING key N behind its key-hash bits (another lock quadrant).  N is inserted by pass 0; then it is only read
     (1 % of a pass) or, n_writes, takes the hot row's own mix at 2 % -- inserted and deleted as well."""
-    hs = _tatp_base()[1][4]
+    hs = tatp_base()[1][4]
     n_key = int(kvkeys.keys_like(CF_HOT[1], hs, 1, same_kh=True, same_quadrant=False, seed=12, key_of=kvkeys.cf_key_of)[0])
     avoid = (tatp_bucket_of(*CF_HOT),)
     rng = np.random.default_rng(6)
@@ -198,7 +198,7 @@ def tatp_cf_pair(p_hot: float, n_writes: bool) -> Case:
     c = Case(W.TATP, dict(n_rows=N_SUB, log_entries=400_000), N_SUB, passes, log_cap=400_000)
     hot_min, ex = {}, []
     for k, n in enumerate(HOT_PASSES):
-        req = _tatp_noise(n, 19 * k + 7, avoid)
+        req = tatp_noise(n, 19 * k + 7, avoid)
         u = rng.random(n)
         _overlay(req, rng, 4, CF_HOT[1], u < p_hot, list(mix), list(mix.values()))
         if k < len(HOT_PASSES) - 1:
@@ -217,7 +217,7 @@ def tatp_cf_pair(p_hot: float, n_writes: bool) -> Case:
 def tatp_rem_pair(hot: int = 7) -> Case:
     """case d: subscriber `hot` is hot; N1 and N2 lie in its bucket in ANOTHER lock quadrant, behind key-hash bits that are each
     other's and not the hot key's: the hot key stays in closed form, the two go through the remainder's chunks in rounds"""
-    hs = _tatp_base()[1][0]
+    hs = tatp_base()[1][0]
     n1 = int(kvkeys.keys_like(hot, hs, 1, same_kh=False, same_quadrant=False, seed=13)[0])
     n2 = int(kvkeys.keys_like(n1, hs, 1, same_kh=True, same_quadrant=True, seed=14, exclude=(hot,))[0])
     avoid = (tatp_bucket_of(0, hot),)
@@ -226,7 +226,7 @@ def tatp_rem_pair(hot: int = 7) -> Case:
     c = Case(W.TATP, dict(n_rows=N_SUB, log_entries=400_000), N_SUB, passes, log_cap=400_000)
     hot_min = {}
     for k, n in enumerate(HOT_PASSES):
-        req = _tatp_noise(n, 23 * k + 9, avoid)
+        req = tatp_noise(n, 23 * k + 9, avoid)
         u = rng.random(n)
         h_sel = u < 0.6
         _overlay(req, rng, 0, hot, h_sel, *TATP_SIMPLE)
@@ -248,7 +248,7 @@ def tatp_rem_pair(hot: int = 7) -> Case:
 def tatp_chunks() -> Case:
     """case a: per table eight groups of three keys behind one (bucket, key hash) and some 130 populated rows, tatp_random over them
     with all eleven op types, well formed -- INSERTs and DELETEs restructure chains that hold colliding keys; cold throughout"""
-    existing, hs = _tatp_base()
+    existing, hs = tatp_base()
     groups = [kvkeys.collision_groups(hs[t], 8, 3, seed=20 + t, key_of=TATP_KEY_OF[t]) for t in range(5)]
     pools = [sorted(set(groups[t].ravel().tolist()) | set(np.sort(existing[t])[:130].tolist())) for t in range(5)]
     req = tracegen.tatp_random(sum(CHUNK_PASSES), existing, seed=41, pools=pools)
@@ -259,7 +259,7 @@ def tatp_chunks() -> Case:
 
 
 # ---- store --------------------------------------------------------------------------------------------------------------------
-def _store_noise(n, seed, avoid_bucket=None):
+def store_noise(n, seed, avoid_bucket=None):
     req = tracegen.store_random(n, seed=seed, n_sub_touch=N_STORE, p_set=0.3, p_missing=0.05)
     if avoid_bucket is not None:  # (the noise stays out of the hot key's bucket)
         hit = kvkeys.np_bucket(req["key"], STORE_HS) == np.uint64(avoid_bucket)
@@ -274,7 +274,7 @@ def store_hot_pair(share: str, exists: bool = True, control: bool = False) -> Ca
     n_key = int(kvkeys.keys_like(STORE_HOT, STORE_HS, 1, same_kh=not control, same_quadrant=None, seed=15)[0])
     hb = int(kvkeys.np_bucket([STORE_HOT], STORE_HS)[0])
     rng = np.random.default_rng(8)
-    first = _store_noise(200, 2, hb)
+    first = store_noise(200, 2, hb)
     if exists:
         first["type"][20], first["key"][20] = S.INSERT, n_key
     passes = [first]
@@ -282,7 +282,7 @@ def store_hot_pair(share: str, exists: bool = True, control: bool = False) -> Ca
     p_h = 0.35 if share == "equal" else 0.6
     hot_min = {}
     for k, n in enumerate(HOT_PASSES):
-        req = _store_noise(n, 17 * k + 6, hb)
+        req = store_noise(n, 17 * k + 6, hb)
         u = rng.random(n)
         h_sel = u < p_h
         _overlay(req, rng, None, STORE_HOT, h_sel, [S.READ, S.SET], [0.7, 0.3])
@@ -306,14 +306,14 @@ def store_rem_pair() -> Case:
     n2 = int(kvkeys.keys_like(n1, STORE_HS, 1, same_kh=True, same_quadrant=None, seed=17, exclude=(STORE_HOT,))[0])
     hb = int(kvkeys.np_bucket([STORE_HOT], STORE_HS)[0])
     rng = np.random.default_rng(9)
-    first = _store_noise(200, 3, hb)
+    first = store_noise(200, 3, hb)
     first["type"][20], first["key"][20] = S.INSERT, n1
     first["type"][50], first["key"][50] = S.INSERT, n2
     passes = [first]
     c = Case(W.STORE, dict(n_rows=N_STORE), N_STORE, passes)
     hot_min = {}
     for k, n in enumerate(HOT_PASSES):
-        req = _store_noise(n, 29 * k + 6, hb)
+        req = store_noise(n, 29 * k + 6, hb)
         u = rng.random(n)
         h_sel = u < 0.6
         _overlay(req, rng, None, STORE_HOT, h_sel, [S.READ, S.SET], [0.7, 0.3])
@@ -364,7 +364,7 @@ SB_ACCT = 200_000
 
 
 @functools.lru_cache(None)
-def _sb_hs(n_acct):
+def sb_hs(n_acct):
     return orc.SmallbankOracle(n_acct, log_entries=16, populate_n=1).hash_size(0)
 
 
@@ -373,16 +373,16 @@ def sb_pair(same_quadrant: bool, populated: bool = True):
     """(H, N, n_acct): two POPULATED accounts of an engine of 200,000 behind one (bucket, key hash) -- or account 7 of an engine of
     2,000 and a searched key that is no account (counted in missing_keys)"""
     if populated:
-        p = kvkeys.colliding_pairs(np.arange(SB_ACCT, dtype=np.uint64), _sb_hs(SB_ACCT), same_quadrant)
+        p = kvkeys.colliding_pairs(np.arange(SB_ACCT, dtype=np.uint64), sb_hs(SB_ACCT), same_quadrant)
         return int(p[0][0]), int(p[0][1]), SB_ACCT
-    n = int(kvkeys.keys_like(7, _sb_hs(2000), 1, same_kh=True, same_quadrant=same_quadrant, seed=18)[0])
+    n = int(kvkeys.keys_like(7, sb_hs(2000), 1, same_kh=True, same_quadrant=same_quadrant, seed=18)[0])
     return 7, n, 2000
 
 
-def _sb_noise(n, seed, n_acct, avoid):
+def sb_noise(n, seed, n_acct, avoid):
     """sb_random over the first 2,000 accounts, kept off the accounts in `avoid`' buckets"""
     req = tracegen.sb_random(n, seed=seed, n_acct_touch=2000)
-    hs = _sb_hs(n_acct)
+    hs = sb_hs(n_acct)
     bad = np.isin(kvkeys.np_bucket(req["key"], hs), kvkeys.np_bucket(np.array(avoid, np.uint64), hs))
     ok = np.nonzero(~np.isin(kvkeys.np_bucket(np.arange(2000, dtype=np.uint64), hs), kvkeys.np_bucket(np.array(avoid, np.uint64), hs)))[0]
     req["key"][bad] = ok[(req["key"][bad] % np.uint64(len(ok))).astype(np.int64)]
@@ -399,7 +399,7 @@ def sb_hot_pair(same_quadrant: bool, share: str, populated: bool = True, both_ro
     hot_rows = [(0, h_key), (1, h_key)] if both_rows else [(0, h_key)]
     mins = [{} for _ in hot_rows]
     for k, n in enumerate(SB_PASSES):
-        req = _sb_noise(n, 50 + k, n_acct, (h_key, n_key))
+        req = sb_noise(n, 50 + k, n_acct, (h_key, n_key))
         u = rng.random(n)
         h_sel = u < 0.6
         for j, (tb, key) in enumerate(hot_rows):
@@ -419,7 +419,7 @@ def sb_hot_pair(same_quadrant: bool, share: str, populated: bool = True, both_ro
 def sb_chunks() -> Case:
     """case a: all seven ops on accounts that collide, both tables -- eight pairs of POPULATED accounts of an engine of 200,000
     (it holds about one triple) and four groups of three keys that are no accounts, among sb_random's noise"""
-    hs = _sb_hs(SB_ACCT)
+    hs = sb_hs(SB_ACCT)
     pop = kvkeys.collision_groups(hs, 8, 2, seed=31, key_of=lambda cand: np.asarray(cand, np.uint64) % np.uint64(SB_ACCT))
     miss = kvkeys.collision_groups(hs, 4, 3, seed=32)
     keys = np.concatenate([pop.ravel(), miss.ravel()])

@@ -359,7 +359,7 @@ def _own_lock_words(keys, hash_size):
 
 
 @functools.lru_cache(None)
-def _lid_maps():
+def lid_maps():
     lids = np.arange(1, 8_000_001, dtype=np.uint32)
     slot = lid_slot(lids)
     o = np.argsort(slot, kind="stable")
@@ -372,7 +372,7 @@ def _lid_maps():
 
 
 def _lid_places(layout, n):
-    first, alias = _lid_maps()
+    first, alias = lid_maps()
     if layout == "spread":
         return _spaced(first[first != 0], n)
     if layout == "alias":
@@ -582,7 +582,7 @@ def cold_edge(name, H) -> Cold:
 
 
 def _localline_lids(n, H):
-    first, _ = _lid_maps()
+    first, _ = lid_maps()
     per = -(-((n + 1) // 2) // H)
     out = []
     for i in range(H):  # global slots g and g + H of home i: locals l and l + 1, l even and both on one line of 16 slots

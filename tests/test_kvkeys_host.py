@@ -26,7 +26,7 @@ def sig(key, hs):
 def hash_size(case, table):
     if case.wl == W.STORE:
         return kc.STORE_HS
-    return kc._tatp_base()[1][table] if case.wl == W.TATP else kc._sb_hs(case.engine["n_rows"])
+    return kc.tatp_base()[1][table] if case.wl == W.TATP else kc.sb_hs(case.engine["n_rows"])
 
 
 def test_key_sig_is_the_oracles_hash():
@@ -79,7 +79,7 @@ def test_collision_groups_share_bucket_and_key_hash(hs, n_groups, per, key_of):
 
 
 def test_colliding_pairs_of_a_populated_table():
-    hs = kc._sb_hs(kc.SB_ACCT)
+    hs = kc.sb_hs(kc.SB_ACCT)
     for same in (False, True):
         p = kvkeys.colliding_pairs(np.arange(kc.SB_ACCT, dtype=np.uint64), hs, same)
         assert len(p) > 50

@@ -38,6 +38,7 @@ SYMBOLS = [
     "dint_state_verify", "dint_state_compact",
     "dint_state_block_digest", "dint_state_block_select", "dint_state_block_rows", "dint_state_block_diff",
     "dint_records_route", "dint_traffic_report",
+    "dint_state_locks", "dint_state_unlock",
 ]
 #: dint_traffic_report: requests / list entries a call takes at most
 TRAFFIC_MAX_N = 1 << 24
@@ -50,6 +51,13 @@ REHASH_DROP_LOCKS = 1
 VERIFY_RECLAIM = 1
 #: dint_state_compact flags
 COMPACT_DRY_RUN = 1
+#: dint_state_unlock flags
+UNLOCK_ALL = 1
+UNLOCK_DRY_RUN = 2
+#: dint_lock_record.flags
+LOCK_KEY_OWNER = 1
+LOCK_KEY_ROW = 2
+LOCK_WALK_CUT = 4
 #: bytes of a table's control block in a TablesView (include/dint_driver.h DINT_VIEW_CTL_BYTES)
 VIEW_CTL_BYTES = 1600
 
@@ -216,6 +224,32 @@ class TableCompact(C.Structure):
         return d
 
 
+class LockStats(C.Structure):
+    """dint_lock_stats (include/dint_abi.h)"""
+    _fields_ = [("total", C.c_uint64), ("held", C.c_uint64 * 5), ("sum_a", C.c_uint64), ("sum_b", C.c_uint64), ("no_row", C.c_uint64),
+                ("walk_cut", C.c_uint64), ("reserved", C.c_uint64 * 6)]
+
+    def as_dict(self) -> dict:
+        return {"total": int(self.total), "held": list(self.held), "sum_a": int(self.sum_a), "sum_b": int(self.sum_b),
+                "no_row": int(self.no_row), "walk_cut": int(self.walk_cut)}
+
+
+class UnlockStats(C.Structure):
+    """dint_unlock_stats (include/dint_abi.h)"""
+    _fields_ = [("released", C.c_uint64), ("stale", C.c_uint64), ("released_a", C.c_uint64), ("released_b", C.c_uint64),
+                ("per_table", C.c_uint64 * 5), ("reserved", C.c_uint64 * 7)]
+
+    def as_dict(self) -> dict:
+        return {"released": int(self.released), "stale": int(self.stale), "released_a": int(self.released_a),
+                "released_b": int(self.released_b), "per_table": list(self.per_table)}
+
+
+class LockGeometry(C.Structure):
+    """struct dint_lock_geometry (include/dint_driver.h)"""
+    _fields_ = [("shard_index", C.c_uint32), ("shard_count", C.c_uint32), ("n_tables", C.c_uint32), ("reserved", C.c_uint32),
+                ("size", C.c_uint64 * 5)]
+
+
 class TableView(C.Structure):
     """dint_table_view (include/dint_driver.h)"""
     _fields_ = [("entries", C.c_void_p), ("n_local", C.c_uint64), ("hash_size", C.c_uint64), ("pool_cap", C.c_uint32),
@@ -320,6 +354,11 @@ def load() -> C.CDLL:
         "dint_state_stats": (C.c_int, [vp, C.POINTER(TableStats), u32, vp]),
         "dint_state_verify": (C.c_int, [vp, C.POINTER(TableVerify), u32, u32, vp]),
         "dint_state_compact": (C.c_int, [vp, C.POINTER(TableCompact), u32, u32, vp]),
+        "dint_state_locks": (i64, [vp, vp, u64, C.POINTER(LockStats), vp]),
+        "dint_state_unlock": (C.c_int, [vp, vp, u64, u32, C.POINTER(UnlockStats), vp]),
+        # include/dint_driver.h: the held locks' rule (csrc/state_locks.h) over an image / a record list in host memory
+        "dint_state_locks_image_host": (i64, [vp, u64, vp, u64, C.POINTER(LockStats)]),
+        "dint_state_unlock_check_host": (u64, [u32, C.POINTER(LockGeometry), vp, u64]),
         # include/dint_driver.h: the replay's classification rule on the host (no device call)
         "dint_log_classify_host": (C.c_int, [vp, u64, vp, vp]),
         # ... and the log ring's words under announcements, cancels and drains (csrc/log_ring.h)

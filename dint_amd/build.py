@@ -11,7 +11,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdint.so")
-SOURCES = ["engine.hip", "k_locks.hip", "k_log.hip", "k_kv.hip", "k_kv_tatp.hip", "k_kv_store.hip", "k_kv_smallbank.hip", "k_route.hip", "k_bench.hip", "k_txn.hip", "k_lock_client.hip", "k_replay.hip", "k_fold.hip", "k_state.hip", "k_block.hip", "k_rroute.hip", "k_image.hip", "k_rehash.hip", "k_load.hip", "k_stats.hip", "k_traffic.hip", "k_verify.hip", "k_compact.hip", "txn_driver.cc",
+SOURCES = ["engine.hip", "k_locks.hip", "k_log.hip", "k_kv.hip", "k_kv_tatp.hip", "k_kv_store.hip", "k_kv_smallbank.hip", "k_route.hip", "k_bench.hip", "k_txn.hip", "k_lock_client.hip", "k_replay.hip", "k_fold.hip", "k_state.hip", "k_block.hip", "k_rroute.hip", "k_image.hip", "k_rehash.hip", "k_load.hip", "k_stats.hip", "k_traffic.hip", "k_verify.hip", "k_compact.hip", "k_locks_state.hip", "txn_driver.cc",
            "fasst_client.cc", "tpl_client.cc"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SHIM = os.path.join(HERE, "dint_udp_server")

@@ -8,6 +8,7 @@
 #include "dint_kv_core.h"
 #include "state_block.h"
 #include "state_image.h"
+#include "state_locks.h"
 #include "state_route.h"
 
 #define DINT_KV_MAX_TABLES 5
@@ -290,6 +291,33 @@ struct dint_rroute_scratch {
 void dint_launch_rroute_count(const rr_geom &g, const void *d_rec, uint64_t n, dint_rroute_scratch s, hipStream_t st);
 // ... then (same stream, the host has seen a good list that fits) the n records into d_out
 void dint_launch_rroute_write(const rr_geom &g, const void *d_rec, uint64_t n, dint_rroute_scratch s, void *d_out, hipStream_t st);
+
+// ---- held locks (k_locks_state.hip; state_locks.h): the held lock units listed, and released by compare and release ---------------
+// the lock units of an engine as the launchers take them (no device memory of its own)
+struct dint_locks_view {
+  lk_geom g;
+  kv_tab tab[DINT_KV_MAX_TABLES];       // kv
+  dint_mod lockmod[DINT_KV_MAX_TABLES]; // ... % (4 * hash_size)
+  uint2 *tbl;                           // lock tables: the local slots
+};
+struct dint_locks_scratch {
+  unsigned long long *words = nullptr;  // [DINT_LOCKS_WORDS] device words: [0] the first record the list is refused at (LK_NO_INDEX: none), [1] the scan's
+                                        // total, [DINT_LOCKS_SUMS_AT + LK_PART r + k] word k of the partials summed over range r (a table)
+  uint32_t *cnt = nullptr;              // [nb] held units per workgroup, all tables in table order ...
+  uint64_t *off = nullptr;              // ... their exclusive scan
+  unsigned long long *part = nullptr;   // [nb][LK_PART] one partial per workgroup (state_locks.h LKS_* / LKU_*)
+  uint64_t nb = 0;
+};
+#define DINT_LOCKS_SUMS_AT 8u
+#define DINT_LOCKS_WORDS (DINT_LOCKS_SUMS_AT + LK_PART * LK_MAX_TABLES)
+uint64_t dint_locks_blocks(const dint_locks_view &v);       // workgroups of the listing and the sweep
+uint64_t dint_locks_list_blocks(uint64_t n);                // ... of the release of a list of n records
+// count, scan, sums and -- d_records != nullptr -- the first `cap` records; the totals into s.words
+void dint_launch_locks_list(const dint_locks_view &v, dint_locks_scratch s, void *d_records, uint64_t cap, hipStream_t st);
+// every held unit released (dry: counted only); the sums into s.words, range = table
+void dint_launch_locks_sweep(const dint_locks_view &v, dint_locks_scratch s, bool dry, hipStream_t st);
+// n > 0: the list checked (s.words[0]), then -- on the device, only for a list that passed -- compare and release; the sums into range 0
+void dint_launch_locks_release(const dint_locks_view &v, dint_locks_scratch s, const void *d_records, uint64_t n, bool dry, hipStream_t st);
 
 // ---- state image (k_image.hip; state_image.h): the tables written out for another shard layout and read back --------
 struct dint_image_scratch {

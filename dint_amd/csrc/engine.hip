@@ -153,6 +153,9 @@ struct dint_engine {
   dint_rroute_scratch rroute{};
   // table report (dint_state_stats): the workgroups' partial reports and the tables' reports, allocated on the first call
   dint_stats_scratch tstats{};
+  // held locks (dint_state_locks / dint_state_unlock): the result words, the workgroups' counts, their scan and their partials;
+  // allocated on first use, grown to what a call needs and kept
+  dint_locks_scratch tlocks{};
   // table verify (dint_state_verify): the owner words, partial reports and reclaim arrays, allocated on the first call and kept
   dint_verify_scratch tverify{};
   hipEvent_t ev_verify[4] = {};  // with dint_timing_enable: before the chain stage, behind it, behind the lists, behind pool stage and sum
@@ -775,6 +778,53 @@ int state_launched() {
   return err == hipSuccess ? 0 : fail(DINT_EHIP, "kernel launch: %s", hipGetErrorString(err));
 }
 
+// held locks: the engine's lock units as the launchers take them, and the scratch (grown to nb workgroups and kept)
+void locks_free(dint_engine *e) {
+  hipFree(e->tlocks.words); hipFree(e->tlocks.cnt); hipFree(e->tlocks.off); hipFree(e->tlocks.part);
+  e->tlocks = dint_locks_scratch{};
+}
+int locks_view(const dint_engine *e, dint_locks_view *v) {
+  memset(v, 0, sizeof *v);
+  lk_geom &g = v->g;
+  g.mode = lk_mode(e->cfg.workload);
+  if (g.mode == LK_NONE) return fail(DINT_ESTATE, "workload has no lock table");
+  g.shard_index = e->shard.index; g.shard_count = e->shard.count ? e->shard.count : 1;
+  if (lk_is_kv(g.mode)) {
+    g.n_tables = e->kv.n_tables;
+    g.same_key = e->kv.h.same_key;
+    for (uint32_t t = 0; t < g.n_tables; t++) {
+      v->tab[t] = e->kv.h.tab[t];
+      v->lockmod[t] = e->kv.h.lockmod[t];
+      g.n_local[t] = e->kv.h.tab[t].n_local;
+      g.size[t] = e->kv.hash_size[t];
+    }
+  } else {
+    g.n_tables = 1;
+    g.n_local[0] = e->n_local_slots;
+    g.size[0] = e->n_slots;
+    v->tbl = e->d_lock_tbl;
+  }
+  return 0;
+}
+int locks_reserve(dint_engine *e, uint64_t nb) {
+  dint_locks_scratch &s = e->tlocks;
+  if (!s.words)
+    if (int rc = dev_alloc((void **)&s.words, DINT_LOCKS_WORDS * sizeof(unsigned long long), false)) return rc;  // (every word a call reads it has written on its stream)
+  if (nb <= s.nb) return 0;
+  hipFree(s.cnt); hipFree(s.off); hipFree(s.part);  // (waits for the device: nothing of an earlier call still reads them)
+  s.cnt = nullptr; s.off = nullptr; s.part = nullptr; s.nb = 0;
+  int rc = dev_alloc((void **)&s.cnt, nb * sizeof(uint32_t), false);
+  if (!rc) rc = dev_alloc((void **)&s.off, nb * sizeof(uint64_t), false);
+  if (!rc) rc = dev_alloc((void **)&s.part, nb * LK_PART * sizeof(unsigned long long), false);
+  if (rc) {
+    hipFree(s.cnt); hipFree(s.off); hipFree(s.part);
+    s.cnt = nullptr; s.off = nullptr; s.part = nullptr;
+    return rc;
+  }
+  s.nb = nb;
+  return 0;
+}
+
 // state image scratch: every array grows to what a call needs and is kept
 void image_free(dint_engine *e) {
   hipFree(e->image.words); hipFree(e->image.blk); hipFree(e->image.blk_off); hipFree(e->image.inl); hipFree(e->image.ovf_src);
@@ -1135,6 +1185,7 @@ void dint_engine_destroy(dint_engine_t *e) {
   rroute_free(e);
   hipFree(e->tstats.part); hipFree(e->tstats.out);
   e->tstats = dint_stats_scratch{};
+  locks_free(e);
   dint_verify_free(e->tverify);
   dint_compact_free(e->tcompact);
   image_free(e);
@@ -1935,6 +1986,81 @@ int dint_state_stats(dint_engine_t *e, dint_table_stats *out, uint32_t cap_table
                   KV_MAX_CHAIN);
   memcpy(out, h, (size_t)e->kv.n_tables * sizeof(dint_table_stats));
   return (int)e->kv.n_tables;
+}
+
+int64_t dint_state_locks(dint_engine_t *e, void *d_records, uint64_t cap, dint_lock_stats *out, void *stream) {
+  if (!e) return fail(DINT_EINVAL, "null engine");
+  if (!d_records && cap) return fail(DINT_EINVAL, "no buffer for %llu records", (unsigned long long)cap);
+  if ((uintptr_t)d_records & 7) return fail(DINT_EINVAL, "lock records need an 8-byte aligned buffer");
+  dint_locks_view v;
+  if (int rc = locks_view(e, &v)) return rc;
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = locks_reserve(e, dint_locks_blocks(v))) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  dint_launch_locks_list(v, e->tlocks, d_records, cap, st);
+  if (int rc = state_launched()) return rc;
+  if (int rc = mark_stream(e, st)) return rc;
+  unsigned long long h[DINT_LOCKS_WORDS];
+  HIP_TRY(hipMemcpyAsync(h, e->tlocks.words, sizeof h, hipMemcpyDeviceToHost, st));  // (the one synchronisation of the call)
+  HIP_TRY(hipStreamSynchronize(st));
+  dint_lock_stats s;
+  memset(&s, 0, sizeof s);
+  s.total = h[1];
+  for (uint32_t t = 0; t < v.g.n_tables; t++) {
+    const unsigned long long *w = h + DINT_LOCKS_SUMS_AT + LK_PART * t;
+    s.held[t] = w[LKS_HELD]; s.sum_a += w[LKS_SUM_A]; s.sum_b += w[LKS_SUM_B]; s.no_row += w[LKS_NO_ROW]; s.walk_cut += w[LKS_WALK_CUT];
+  }
+  if (out) *out = s;
+  return (int64_t)(d_records ? std::min<uint64_t>(cap, s.total) : 0);
+}
+
+int dint_state_unlock(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t flags, dint_unlock_stats *out, void *stream) {
+  if (!e) return fail(DINT_EINVAL, "null engine");
+  if (flags & ~(DINT_UNLOCK_ALL | DINT_UNLOCK_DRY_RUN)) return fail(DINT_EINVAL, "unknown flags %#x", flags);
+  const bool all = (flags & DINT_UNLOCK_ALL) != 0, dry = (flags & DINT_UNLOCK_DRY_RUN) != 0;
+  if (all && (d_records || n)) return fail(DINT_EINVAL, "DINT_UNLOCK_ALL takes no list");
+  if (!all && !d_records && n) return fail(DINT_EINVAL, "no list of %llu records", (unsigned long long)n);
+  if ((uintptr_t)d_records & 7) return fail(DINT_EINVAL, "lock records need an 8-byte aligned buffer");
+  if (n >= LK_MAX_LIST) return fail(DINT_EINVAL, "a list of %llu records: fewer than 2^32 - 16 at a time", (unsigned long long)n);
+  dint_locks_view v;
+  if (int rc = locks_view(e, &v)) return rc;
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (int rc = state_quiet(e)) return rc;
+  dint_unlock_stats s;
+  memset(&s, 0, sizeof s);
+  if (!all && n == 0) {
+    if (out) *out = s;
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = locks_reserve(e, all ? dint_locks_blocks(v) : dint_locks_list_blocks(n))) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  if (int rc = order_stream(e, st)) return rc;
+  if (all) dint_launch_locks_sweep(v, e->tlocks, dry, st);
+  else dint_launch_locks_release(v, e->tlocks, d_records, n, dry, st);
+  if (int rc = state_launched()) return rc;
+  if (int rc = mark_stream(e, st)) return rc;
+  unsigned long long h[DINT_LOCKS_WORDS];
+  HIP_TRY(hipMemcpyAsync(h, e->tlocks.words, sizeof h, hipMemcpyDeviceToHost, st));  // (the one synchronisation: verdict and counts)
+  HIP_TRY(hipStreamSynchronize(st));
+  const unsigned long long *w = h + DINT_LOCKS_SUMS_AT;
+  if (all) {
+    for (uint32_t t = 0; t < v.g.n_tables; t++, w += LK_PART) {
+      s.per_table[t] = w[LKS_HELD]; s.released += w[LKS_HELD]; s.released_a += w[LKS_SUM_A];
+      s.released_b += v.g.mode == LK_FASST ? 0 : w[LKS_SUM_B];
+    }
+  } else {
+    if (h[0] != LK_NO_INDEX)
+      return fail(DINT_EINVAL, "record %llu: a table or slot the engine has not, a record that holds nothing, or not strictly ascending in (table, "
+                               "bucket, q); nothing was released", h[0]);
+    for (uint32_t t = 0; t < LK_MAX_TABLES; t++) { s.per_table[t] = w[LKU_TABLE + t]; s.released += w[LKU_TABLE + t]; }
+    s.stale = w[LKU_STALE]; s.released_a = w[LKU_REL_A]; s.released_b = w[LKU_REL_B];
+  }
+  if (out) *out = s;
+  return 0;
 }
 
 int dint_state_verify(dint_engine_t *e, dint_table_verify *out, uint32_t cap_tables, uint32_t flags, void *stream) {

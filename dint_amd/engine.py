@@ -16,6 +16,15 @@ import numpy as np
 from . import _lib
 from .wire import LOG_REC, MSG_DTYPE, Workload
 
+#: dint_lock_record (include/dint_abi.h): one held lock unit
+LOCK_REC = np.dtype([("slot", "<u8"), ("a", "<u4"), ("b", "<u4"), ("key", "<u8"), ("cand_rows", "<u4"), ("table", "u1"), ("flags", "u1"),
+                     ("zero", "<u2")])
+
+
+def lock_records(t, n: int) -> np.ndarray:
+    """the first n records of a state_locks tensor as a numpy array of LOCK_REC (a copy in host memory)"""
+    return t.reshape(-1)[:32 * n].cpu().numpy().view(LOCK_REC).copy()
+
 
 _N_TABLES = {Workload.STORE: 1, Workload.TATP: 5, Workload.SMALLBANK: 2}
 
@@ -452,6 +461,35 @@ class Engine:
         self.last_compact_stage_ns = dict(zip(("census", "count", "move", "commit"), list(s[0].reserved)[:4]))  # with timing_enable on
         n = _lib.check(rc)
         return self.last_compact[:n]
+
+    # ---- held locks (dint_state_locks / dint_state_unlock) ----------------------------------------------------
+    def state_locks(self, d_buf=None, cap: int = 0, stream: int = 0):
+        """dint_state_locks: the lock units this engine holds as 32-byte records (LOCK_REC; include/dint_abi.h
+        dint_lock_record, csrc/state_locks.h is the rule) in the HBM buffer d_buf (room for cap records, 8-byte aligned; a
+        torch tensor or a device pointer), in the order table, local bucket, q (lock tables: local slot).  d_buf=None counts
+        first and allocates a uint8 tensor [records, 32] on this engine's device.  Returns (records tensor, records written,
+        stats); stats["total"] is the number there are, "held" per table.  Nothing is modified.  `lock_records(t, n)` turns
+        the tensor into a numpy array of LOCK_REC."""
+        import torch
+
+        s = _lib.LockStats()
+        if d_buf is None:
+            _lib.check(self._L.dint_state_locks(self._h, None, 0, C.byref(s), stream))  # (counts only)
+            cap = int(s.total)
+            d_buf = torch.empty((max(cap, 1), 32), dtype=torch.uint8, device=self._torch_device())
+        n = _lib.check(self._L.dint_state_locks(self._h, _ptr(d_buf), cap, C.byref(s), stream))
+        return d_buf, n, s.as_dict()
+
+    def state_unlock(self, d_records=None, n: int = 0, all: bool = False, dry_run: bool = False, stream: int = 0) -> dict:
+        """dint_state_unlock: compare and release.  The n records of state_locks' form and order in the HBM buffer d_records
+        (its output or any sub-sequence) are checked as a whole, then each unit is released only if it still holds what its
+        record says -- the others are counted "stale"; all=True releases every held unit instead; dry_run=True gives the same
+        check and counts and writes nothing.  Returns released, stale, released_a, released_b, per_table.  Raises DintError
+        (DINT_EINVAL) with nothing released for a list that is not one; the message names the first bad record."""
+        s = _lib.UnlockStats()
+        flags = (_lib.UNLOCK_ALL if all else 0) | (_lib.UNLOCK_DRY_RUN if dry_run else 0)
+        _lib.check(self._L.dint_state_unlock(self._h, None if d_records is None else _ptr(d_records), n, flags, C.byref(s), stream))
+        return s.as_dict()
 
     # ---- traffic report (dint_traffic_report) ----------------------------------------------------------------
     def traffic_report(self, d_reqs, n: int, d_replies=None, top: int = 16, stream: int = 0) -> dict:

@@ -36,6 +36,10 @@ beside the digest's flat one.
 All of it assumes structurally sound tables.  `verify_tables` checks that on a shard set (dint_state_verify;
 csrc/k_verify.hip): the census of chains, free lists, pend lists and pool added up, `ok` / `clean`, and on request the leaked
 pool entries put back on the free lists.
+
+The lock words are the part of a server's state a crashed client leaves in a bad state: a coordinator that dies between ACQUIRE
+and COMMIT / ABORT leaves its locks held for good.  `held_locks` lists what a shard set holds, with global ids (dint_state_locks;
+csrc/k_locks_state.hip), and `release_locks` sets the listed units -- or all -- free by compare and release (dint_state_unlock).
 """
 from __future__ import annotations
 
@@ -296,7 +300,9 @@ def rehash(src_engines, dst_engines, drop_locks: bool = False) -> dict:
     with their own n_rows, pool_entries and shard layout: every destination takes all sources (Engine.state_rehash) and keeps
     the rows that are home to it.  With a complete destination set (shard j of H at position j) every row lands exactly once;
     this is checked -- the placed rows sum to the sources' rows and the summed digests are equal -- and DintError is raised
-    otherwise.  Sources that hold lock words are refused unless drop_locks (a lock word belongs to a slot of the old size).
+    otherwise.  Sources that hold lock words are refused unless drop_locks (a lock word belongs to a slot of the old size);
+    `held_locks(src_engines)` shows which units a refusal is about -- slot, counters, owner or candidate key -- and
+    `release_locks(src_engines, records)` sets the orphaned ones free, after which the rehash goes through without dropping any.
     The sources are only read; their log rings are not moved (drain them first).  Returns {rows_seen, rows_placed,
     locks_held, tables: per table {rows, overflow_entries, longest_chain} over the destinations, per_engine: [stats]}.
 
@@ -319,6 +325,73 @@ def rehash(src_engines, dst_engines, drop_locks: bool = False) -> dict:
         raise DintError(f"rehash: the destinations placed {tot['rows_placed']} of the sources' {tot['rows_seen']} rows: not a complete shard set")
     if digest_sum(src_engines) != digest_sum(dst_engines):
         raise DintError("rehash: the destinations' digests do not add up to the sources'")
+    return tot
+
+
+#: a row of held_locks: dint_lock_record's fields plus where the unit lives in the set and its GLOBAL ids
+HELD_LOCK = np.dtype([("shard", "<u4"), ("slot", "<u8"), ("a", "<u4"), ("b", "<u4"), ("key", "<u8"), ("cand_rows", "<u4"), ("table", "u1"),
+                      ("flags", "u1"), ("q", "u1"), ("bucket", "<u8"), ("lock_hash", "<u8")])
+
+
+def held_locks(engines) -> np.ndarray:
+    """The lock units a set of engines holds (Engine.state_locks per engine), merged into one numpy array of HELD_LOCK in set
+    order: `shard` = the engine's position, slot / a / b / key / cand_rows / table / flags as the engine reported them, and the
+    GLOBAL ids added.  Lock tables: bucket = lock_hash = the global slot, local * H + index.  tatp / smallbank: q = the unit's
+    quadrant, bucket = the global bucket local * H + index, lock_hash = q * hash_size + bucket -- what fasthash64(key) %
+    (4 * hash_size) of every key that can hold the unit is.  H and index are each engine's own shard_count and shard_index."""
+    from .engine import lock_records
+
+    out = []
+    for pos, e in enumerate(engines):
+        buf, n, _ = e.state_locks()
+        r = lock_records(buf, n)
+        h = np.zeros(n, HELD_LOCK)
+        for k in ("slot", "a", "b", "key", "cand_rows", "table", "flags"):
+            h[k] = r[k]
+        h["shard"] = pos
+        H, i = np.uint64(e.shard_count), np.uint64(e.shard_index)
+        if e.workload in (Workload.TATP, Workload.SMALLBANK):
+            hs = np.array([e.hash_size(int(t)) for t in r["table"]], np.uint64)
+            n_local = (hs + H - np.uint64(1)) // H
+            q = r["slot"] // np.maximum(n_local, np.uint64(1))
+            h["q"] = q
+            h["bucket"] = (r["slot"] - q * n_local) * H + i
+            h["lock_hash"] = q * hs + h["bucket"]
+        else:
+            h["bucket"] = h["lock_hash"] = r["slot"] * H + i
+        out.append(h)
+    return np.concatenate(out) if out else np.zeros(0, HELD_LOCK)
+
+
+def release_locks(engines, records=None, dry_run: bool = False) -> dict:
+    """Release lock units of a set of engines.  records=None: every held unit of every engine (Engine.state_unlock(all=True)).
+    Otherwise `records` = rows of held_locks over THIS set, in any selection that keeps each shard's rows in their order: per
+    shard they are uploaded and released by compare and release, so a unit that was released and taken again since the listing
+    is left alone and counted "stale".  dry_run=True only counts.  Returns {released, stale, released_a, released_b,
+    per_table, per_engine: [Engine.state_unlock's dict]}; a shard's list that is refused raises DintError, nothing of THAT
+    shard released."""
+    import torch
+
+    from .engine import LOCK_REC
+
+    engines = list(engines)
+    per = []
+    for pos, e in enumerate(engines):
+        if records is None:
+            per.append(e.state_unlock(all=True, dry_run=dry_run))
+            continue
+        mine = records[records["shard"] == pos]
+        rec = np.zeros(len(mine), LOCK_REC)
+        for k in ("slot", "a", "b", "key", "cand_rows", "table", "flags"):
+            rec[k] = mine[k]
+        if len(rec) == 0:
+            per.append(e.state_unlock(None, 0, dry_run=dry_run))
+            continue
+        d = torch.from_numpy(rec.view(np.uint8).copy()).to(e._torch_device())
+        per.append(e.state_unlock(d, len(rec), dry_run=dry_run))
+    tot = {k: sum(p[k] for p in per) for k in ("released", "stale", "released_a", "released_b")}
+    tot["per_table"] = [sum(p["per_table"][t] for p in per) for t in range(5)]
+    tot["per_engine"] = per
     return tot
 
 

@@ -782,6 +782,71 @@ struct dint_traffic_report { /* (a struct tag only: the call below has the name)
  * (DINT_EINVAL); a log_server engine (DINT_ESTATE). */
 int dint_traffic_report(dint_engine_t *e, const void *d_reqs, const void *d_replies, uint64_t n, uint32_t top_k,
                         struct dint_traffic_report *out, dint_traffic_key *by_requests, dint_traffic_key *by_rejects, void *stream);
+/* ---- held locks (v5, additive): which lock units a server holds, and the release of orphaned ones -- where they lie -----------
+ * A coordinator that dies between ACQUIRE and COMMIT / ABORT leaves its locks held for good: no release checks an owner, and from
+ * then on every request on the slot is answered REJECT.  dint_state_locks lists the held units from the device, dint_state_unlock
+ * releases the listed ones -- or all -- by compare and release (dint_amd/csrc/state_locks.h is the rule).  lock_fasst, lock_2pl, tatp
+ * and smallbank engines, sharded or not; store and log_server: DINT_ESTATE.
+ *   unit, held iff:  lock_fasst  d_lock_tbl[local slot] = {lock, ver}: lock != 0 (a non-zero version alone is not a held lock)
+ *                    lock_2pl    {num_ex, num_sh}: either non-zero
+ *                    tatp        byte q of the lock word of local bucket l's inline header: non-zero
+ *                    smallbank   pair q of the counters of local bucket l's inline entry: either word non-zero */
+#define DINT_LOCK_KEY_OWNER 1u /* dint_lock_record.flags: tatp with DINT_FLAG_LOCK_SAME_KEY -- key is the recorded owner of the unit */
+#define DINT_LOCK_KEY_ROW 2u   /* otherwise, cand_rows > 0: key is the first candidate row in chain order */
+#define DINT_LOCK_WALK_CUT 4u  /* the chain walk stopped at its bound (4096 entries), at a second visit of the inline entry or at a link
+                                  outside the pool (dint_state_block_digest's bound and link check): cand_rows is what was seen up to there */
+typedef struct dint_lock_record {
+  uint64_t slot;      /* the LOCAL slot index exactly as dint_read_locks numbers it: lock tables global slot / shard_count; kv q * n_local + local bucket */
+  uint32_t a, b;      /* as dint_read_locks: {lock, ver}, {num_ex, num_sh}, {lock byte, 0} */
+  uint64_t key;       /* see flags; 0 when neither KEY flag is set (always for the lock tables: a lid is not stored) */
+  uint32_t cand_rows; /* kv: valid slots in the chain of the unit's bucket whose key's lock slot is this unit, fasthash64(key) % (4 * hash_size)
+                         == q * hash_size + global bucket; shadowed duplicates count, holes do not */
+  uint8_t table, flags;
+  uint16_t zero;
+} dint_lock_record;
+typedef struct dint_lock_stats {
+  uint64_t total;        /* held units in all (also when cap cut the list) */
+  uint64_t held[5];      /* ... per table (= dint_table_stats.locks_held) */
+  uint64_t sum_a, sum_b; /* over the held units: lock_2pl / smallbank the exclusive and the shared holders */
+  uint64_t no_row;       /* kv units with cand_rows == 0 */
+  uint64_t walk_cut;     /* kv units with DINT_LOCK_WALK_CUT */
+  uint64_t reserved[6];
+} dint_lock_stats;
+/* (v5, additive) the held units as 32-byte records into d_records (DEVICE memory, 8-byte aligned, room for cap records), in the order
+ * ascending table, then ascending local bucket, then ascending q (lock tables: ascending local slot); returns the records written
+ * = the first `cap` of that order, out->total says how many there are.  d_records == NULL with cap == 0 only counts.  Positions come
+ * from a count per workgroup, a scan and wave ballots -- no atomic decides one, two calls write the same bytes.  Synchronous like
+ * dint_state_stats: ordered behind the engine's pending work on `stream` (NULL = the engine's own), one host synchronisation.
+ * Read-only: tables, lock words, dint_stats, the log ring and its cursor stay as they were, a blank engine stays blank and a fresh
+ * table fresh.  Refused: a store / log_server engine, a batch announced by dint_submit_device_ahead pending (DINT_ESTATE); a
+ * misaligned buffer, d_records == NULL with cap > 0 (DINT_EINVAL).  No content of the tables makes the kernels read outside them or
+ * write outside the cap records.  The caller keeps the engine quiet meanwhile. */
+int64_t dint_state_locks(dint_engine_t *e, void *d_records, uint64_t cap, dint_lock_stats *out, void *stream);
+#define DINT_UNLOCK_ALL 1u     /* dint_state_unlock flags: every held unit (d_records == NULL, n == 0) */
+#define DINT_UNLOCK_DRY_RUN 2u /* the same check, counts and return value; nothing is written */
+typedef struct dint_unlock_stats {
+  uint64_t released;               /* units set free (dry run: that would be) */
+  uint64_t stale;                  /* list form: units left alone because they no longer hold what their record says */
+  uint64_t released_a, released_b; /* the counter sums given up (lock_fasst: a only) */
+  uint64_t per_table[5];           /* released, per table */
+  uint64_t reserved[7];
+} dint_unlock_stats;
+/* (v5, additive) LIST FORM: n records of dint_state_locks' form and order in DEVICE memory (8-byte aligned) -- its output or any
+ * sub-sequence of it.  The whole list is read before a byte is written and refused with DINT_EINVAL, tables untouched and
+ * dint_last_error naming the first such index, for: a table the workload has not; a slot outside the engine's local range, or on a
+ * sharded kv engine a unit whose global bucket lies beyond the table; records not strictly ascending in (table, bucket, q); a record
+ * with a == 0 && b == 0 (lock_fasst: a == 0).  Then COMPARE AND RELEASE, one lane per record: a unit is released only if its
+ * current {a, b} equals the record's (lock_fasst: a alone, the version moves independently) and, for a record with
+ * DINT_LOCK_KEY_OWNER on a DINT_FLAG_LOCK_SAME_KEY engine, the stored owner key equals the record's key; otherwise it is left alone
+ * and counted `stale` (released and taken again since the listing, or free by now).  key without KEY_OWNER, cand_rows and the other
+ * flags of an input record are ignored.  DINT_UNLOCK_ALL: a sweep over the listing's ranges releases every held unit.  A release
+ * writes what the workload's own release leaves: lock_fasst lock = 0, version untouched; lock_2pl / smallbank both counters 0; tatp
+ * the one lock byte 0 by a byte store, the owner key left as an ABORT leaves it.  Never written: rows, versions, valid bytes,
+ * links, the pool, the log ring and its cursor, dint_stats, the blank and the freshness gates.  Synchronous, ordered as
+ * dint_state_locks, one host synchronisation (the releasing kernel reads the check's verdict on the device).  Returns 0.  Refused
+ * besides: unknown flags, DINT_UNLOCK_ALL with a list, a NULL list with n > 0, a misaligned buffer, n >= 2^32 - 16 (DINT_EINVAL); a
+ * store / log_server engine, an announced batch pending (DINT_ESTATE).  The caller keeps the engine quiet meanwhile. */
+int dint_state_unlock(dint_engine_t *e, const void *d_records, uint64_t n, uint32_t flags, dint_unlock_stats *out, void *stream);
 int dint_get_stats(dint_engine_t *e, dint_stats *out);
 /* reset tables, locks, log and stats to the freshly-created (unpopulated) state */
 int dint_reset(dint_engine_t *e);

@@ -243,6 +243,27 @@ int dint_state_image_check_host(const void *image, uint64_t bytes);
 struct dint_table_stats; /* include/dint_abi.h */
 int dint_state_stats_image_host(const void *image, uint64_t bytes, struct dint_table_stats *out, uint32_t cap_tables);
 
+/* ---- held locks: the rule on the host (dint_amd/csrc/state_locks.h) -----------------------------------------------------
+ * dint_state_locks (include/dint_abi.h) over a state image in HOST memory: the held units of the image as records[0 .. cap) (any
+ * alignment; NULL with cap == 0 only counts), in the call's order, `slot` the local index of the image's SOURCE (src_index,
+ * src_count); returns the records written, out->total how many there are.  The image first goes through
+ * dint_state_image_check_host: a malformed one is refused with DINT_EINVAL and nothing is walked.  Images of the lock tables are
+ * taken (they hold the slots); a store image: DINT_ESTATE.  An engine's OWN image -- (shard_index, shard_count) exported to that
+ * same pair -- gives the device's list record for record (but for a sharded engine's last local bucket where it lies beyond the
+ * table's global size: an image leaves that bucket out, and it holds no lock).  No device call. */
+struct dint_lock_record; /* include/dint_abi.h */
+struct dint_lock_stats;
+int64_t dint_state_locks_image_host(const void *image, uint64_t bytes, struct dint_lock_record *records, uint64_t cap, struct dint_lock_stats *out);
+/* The list check of dint_state_unlock alone, over n records in HOST memory (any alignment): the index of the first record the call
+ * would refuse the list at, or n when there is none.  geometry = the engine's: its shard and per table the GLOBAL size (lock tables:
+ * n_slots, one table; kv: dint_hash_size of every table).  A workload without lock units has no table: 0 for any n > 0.  No device call. */
+struct dint_lock_geometry {
+  uint32_t shard_index, shard_count; /* count 0 or 1: unsharded */
+  uint32_t n_tables, reserved;
+  uint64_t size[5];
+};
+uint64_t dint_state_unlock_check_host(uint32_t workload, const struct dint_lock_geometry *geometry, const struct dint_lock_record *records, uint64_t n);
+
 /* ---- rehash: the layout rule on the host (dint_amd/csrc/state_rehash.h) -----------------------------------------------
  * Where dint_state_rehash (include/dint_abi.h) puts the rows of ONE table, restated for tests and tools: keys[0 .. n) = the
  * keys of the sources' rows in SOURCE ORDER (the sources' dint_dump_rows, concatenated in srcs order), hash_size = the

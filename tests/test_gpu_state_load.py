@@ -14,6 +14,7 @@ from dint_amd import _lib, wire
 from dint_amd.engine import Engine
 from dint_amd import recovery
 from kvkeys import keys_by_bucket, np_bucket, overflow_need, raw_submit
+from load_helpers import dev, load_dev, pool_need, rows_host, same_state
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -22,50 +23,6 @@ EINVAL, ENOMEM, ESTATE = -1, -2, -5
 N_TABLES = {W.STORE: 1, W.TATP: 5, W.SMALLBANK: 2}
 N_POP = 2500
 PER = [0, 1, 4, 5, 8, 9, 41]
-
-
-def rows_host(wl, table, n):
-    """the population's rows of one table through the rule on the host (no device call)"""
-    L = _lib.load()
-    vs = 8 if wl == W.SMALLBANK else 40
-    m = L.dint_populate_rows_host(int(wl), table, 0, n, None, None, 0)
-    keys = np.zeros(m, "<u8"); vals = np.zeros((m, vs), "u1")
-    assert L.dint_populate_rows_host(int(wl), table, 0, n, keys.ctypes.data, vals.ctypes.data, m) == m
-    return keys, vals
-
-
-def pool_need(wl, n_rows, n_pop, shard=(0, 1)):
-    """the overflow entries the fullest table of the population needs (kvkeys.overflow_need over the rows per local bucket)"""
-    need = 0
-    for t, hs in enumerate(recovery.hash_sizes(wl, n_rows)):
-        g = np_bucket(rows_host(wl, t, n_pop)[0], hs).astype(np.int64)
-        g = g[g % shard[1] == shard[0]] // shard[1]
-        need = max(need, overflow_need(np.bincount(g, minlength=-(-hs // shard[1]))))
-    return need
-
-
-def same_state(a, b):
-    """every comparison the twins must pass"""
-    for t in range(N_TABLES[a.workload]):
-        x, y = a.dump_rows(t), b.dump_rows(t)
-        assert all(p.shape == q.shape and (p == q).all() for p, q in zip(x, y)), ("rows differ", t, len(x[0]), len(y[0]))
-        if a.workload != W.STORE:  # (the store keeps no lock words)
-            assert not a.read_locks(t)[0].any() and not a.read_locks(t)[1].any()
-    assert a.state_digest() == b.state_digest()
-    assert a.state_stats() == b.state_stats()
-    for r in a.state_verify():
-        bad = {k: v for k, v in r.items() if k in ("bad_chains", "cross_linked", "linked_beyond_top", "list_bad_links", "stray_valid_entries",
-                                                   "stray_rows", "misplaced_rows", "odd_valid_bytes", "unaccounted") and v}
-        assert not bad, r
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.int64 if x.dtype == np.uint64 else np.int32 if x.dtype == np.uint32 else x.dtype)).cuda()
-
-
-def load_dev(e, table, keys, vers, vals):
-    return e.load_rows_device(table, dev(keys), None if vers is None else dev(vers), dev(vals))
-
 
 SHAPES = [(W.TATP, 64, N_POP, None), (W.STORE, 64, N_POP, None), (W.SMALLBANK, 64, N_POP, None), (W.TATP, 20000, 20000, 0)]
 

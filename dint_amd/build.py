@@ -17,10 +17,16 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SHIM = os.path.join(HERE, "dint_udp_server")
 CLIENT = os.path.join(HERE, "dint_udp_client")  # closed-loop loopback load generator (csrc/udp_loop_client.c)
 ROCM_LIB = os.environ.get("ROCM_LIB", "/opt/rocm/lib")
+# The GPU-resident transaction clients (csrc/k_txn.hip) a second time, for tests only: workgroups of TXN_SMALL_TB clients.  The
+# look-back of k_txn_emit covers a workgroup's worth of earlier workgroups per step, and at the product's 512 no more workgroups
+# are resident than one step covers; at 128 (two waves) thousands are, and a walk takes many steps.
+TXN_SMALL_TB = 128
+TXN_SMALL_LIB = os.path.join(HERE, "libdint_txn_small.so")
+TXN_SMALL_SOURCES = ["txn_driver.cc"]  # what k_txn.hip needs beside itself
 
 
 def _stale() -> bool:
-    if not os.path.exists(LIB) or not os.path.exists(SHIM) or not os.path.exists(CLIENT):
+    if not all(os.path.exists(p) for p in (LIB, SHIM, CLIENT, TXN_SMALL_LIB)):
         return True
     t = os.path.getmtime(LIB)
     inc = os.path.join(HERE, "..", "include")
@@ -57,13 +63,16 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return (not force and not flags and os.path.exists(obj) and os.path.getmtime(obj) > max(t_h, os.path.getmtime(src)))
 
     jobs = [(os.path.join(CSRC, s), os.path.join(objdir, os.path.splitext(s)[0] + ".o"), flags, verbose) for s in SOURCES]
+    jobs.append((os.path.join(CSRC, "k_txn.hip"), os.path.join(objdir, "k_txn_small.o"), flags + [f"-DTXG_TB={TXN_SMALL_TB}u"], verbose))
     jobs = [j + (fresh(j[0], j[1]),) for j in jobs]
     with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
         objs = list(ex.map(_compile, jobs))
-    cmd = [HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB] + objs
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
+    small = [objs.pop()] + [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in TXN_SMALL_SOURCES]
+    for cmd in ([HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB] + objs,
+                [HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-Wl,--no-undefined", "-o", TXN_SMALL_LIB] + small):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
     # the UDP host shim (plain C) links against the library it sits next to
     shim = [os.environ.get("CC", "gcc"), "-std=gnu11", "-O2", "-Wall", "-o", SHIM, os.path.join(CSRC, "udp_shim.c"),
             "-L" + HERE, "-ldint", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + ROCM_LIB, "-lpthread"]

@@ -30,7 +30,15 @@
 #include "dint_device.h"
 #include "txn_clients.h"
 
+// A look-back step covers TXG_TB workgroups, and an MI355X holds at most 512 workgroups of k_txn_emit at once (256 CUs, two
+// each: 8 waves a workgroup against at most 5 per SIMD, 48 - 70 KB of LDS against 160): every workgroup before mine that has
+// not published its prefix is resident, so a walk ends within ONE step and the loop's further steps never run in this build.
+// dint_amd/build.py compiles this file a second time with a smaller TXG_TB (libdint_txn_small.so: thousands of resident
+// workgroups, walks of many steps) for tests/test_gpu_client_edges.py.
+#ifndef TXG_TB
 #define TXG_TB 512u   // clients per workgroup (256: 408 us per closed-loop epoch, 512: 392, 1024: 419 -- fewer tickets and look-back entries against fewer resident workgroups)
+#endif
+static_assert(TXG_TB % 64 == 0 && TXG_TB >= 64 && TXG_TB <= 1024, "whole waves, one workgroup");
 #define TXG_AGG 0x40000000u  // look-back word: the workgroup's own message count ...
 #define TXG_PFX 0x80000000u  // ... or the count of all workgroups up to and including it
 #define TXG_VAL 0x3FFFFFFFu

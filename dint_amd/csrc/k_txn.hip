@@ -20,6 +20,10 @@
 //                   loop does) this is FUSED into k_txn_emit instead: the epoch's batches alternate between two buffer
 //                   sets, so a client reads the replies of epoch k from one set while the requests of epoch k+1 are
 //                   written into the other -- one kernel and one header load per epoch less.
+//   latency       : with DINT_DRIVER_LATENCY the LAT = true instantiation of k_txn_emit is launched: it leaves the epoch's
+//                   clock stamp in a ring and adds the finished transactions' round trips and ticks (txn_latency.h) to the
+//                   driver's dint_driver_latency -- LDS counters first, one device atomic per non-zero counter and workgroup.
+//                   It only observes: the request stream is the same bytes.  LAT = false is the kernel without any of it.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -29,6 +33,7 @@
 #include "../../include/dint_driver.h"
 #include "dint_device.h"
 #include "txn_clients.h"
+#include "txn_latency.h"
 
 // A look-back step covers TXG_TB workgroups, and an MI355X holds at most 512 workgroups of k_txn_emit at once (256 CUs, two
 // each: 8 waves a workgroup against at most 5 per SIMD, 48 - 70 KB of LDS against 160): every workgroup before mine that has
@@ -75,18 +80,31 @@ __device__ static inline void txg_store_client(const C &c, uint32_t *cols, uint3
     if (!txg_is_m<C>(j)) cols[(size_t)j * n_clients + i] = w[j];
 }
 
+#define TXG_NLAT (2u * 8u * LAT_RT_BINS)  // LDS latency counters of a workgroup: committed / aborted x type x min(r, 31)
+typedef unsigned long long txg_u64;
+
 // W = waves per SIMD the kernel is compiled for (the register budget: 3 -> 168, 4 -> 128, 5 -> 96 VGPRs; DINT_TXN_WAVES)
-template <class T, int W>
+// LAT = keep the transaction latency (lat, ring, epoch: the driver's histograms, its epoch stamps, the number of this epoch)
+template <class T, int W, bool LAT>
 __global__ void __launch_bounds__(TXG_TB, W)
 k_txn_emit(uint32_t *cl, uint8_t *store, uint32_t n_clients, TxParams P, uint8_t *out0, uint8_t *out1,
            uint8_t *out2, const uint8_t *rep0, const uint8_t *rep1, const uint8_t *rep2, uint32_t cap, uint32_t *pub,
-           uint32_t *ticket, uint32_t *pub_other, uint32_t *ticket_other, uint32_t *counts, txg_stats *st, uint32_t dbg) {
+           uint32_t *ticket, uint32_t *pub_other, uint32_t *ticket_other, uint32_t *counts, txg_stats *st, uint32_t dbg,
+           dint_driver_latency *lat, uint64_t *ring, uint64_t epoch) {
   typedef typename T::Msg Msg;
   __shared__ uint32_t Stile, Sw[3][TXG_TB / 64];
   __shared__ unsigned long long Sst[TXG_NSTAT];
+  __shared__ uint32_t Slat[LAT ? TXG_NLAT : 1];  // (referenced under LAT only: without it the array is not allocated)
+  __shared__ uint64_t Snow;
   const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) Stile = atomicAdd(ticket, 1u);
+  if (t == 0) {
+    const uint32_t tk = atomicAdd(ticket, 1u);
+    Stile = tk;
+    // the epoch's stamp: the first workgroup the kernel hands out, before anything else
+    if constexpr (LAT) { if (tk == 0) ring[epoch & (LAT_RING - 1)] = __builtin_amdgcn_s_memrealtime(); }
+  }
   if (t < TXG_NSTAT) Sst[t] = 0;
+  if constexpr (LAT) { for (uint32_t j = t; j < TXG_NLAT; j += TXG_TB) Slat[j] = 0; }
   __syncthreads();
   const uint32_t tile = Stile, i = tile * TXG_TB + t, ntiles = gridDim.x;
   const bool valid = i < n_clients;
@@ -230,10 +248,38 @@ k_txn_emit(uint32_t *cl, uint8_t *store, uint32_t n_clients, TxParams P, uint8_t
         atomicAdd(&Sst[offsetof(txg_stats, committed) / 8], 1ull);
         atomicAdd(&Sst[offsetof(txg_stats, committed_by_type) / 8 + o.fin_txn[k]], 1ull);
       }
+      if constexpr (LAT) {
+        const uint32_t ty = o.fin_txn[k] & 7u, r = o.fin_rt[k];
+        atomicAdd(&Slat[((o.fin_ok[k] ? 0u : 1u) * 8u + ty) * LAT_RT_BINS + lat_rt_bin(r)], 1u);
+        if (o.fin_ok[k] && r > LAT_RT_BINS - 1) {  // beyond the last bin: what the counter's index cannot say, straight to HBM
+          atomicAdd((txg_u64 *)&lat->rt_sum[ty], (txg_u64)(r - (LAT_RT_BINS - 1)));
+          atomicMax((txg_u64 *)&lat->rt_max[ty], (txg_u64)r);
+        }
+      }
     }
   }
+  if constexpr (LAT) { if (t == 0) Snow = __builtin_amdgcn_s_memrealtime(); }  // the workgroup's clock, read once
   __syncthreads();
   if (t < TXG_NSTAT && Sst[t]) atomicAdd((unsigned long long *)st + t, Sst[t]);
+  if constexpr (LAT) {
+    // one thread per non-zero counter.  The epoch a transaction of r round trips began in is epoch - r; its stamp was
+    // written by an earlier kernel of this driver (kernel boundaries order it), so within a workgroup and an epoch the
+    // tick latency is a function of r alone.  (r is the bin's: beyond 31 round trips a transaction is timed from epoch - 31.)
+    const uint64_t now = Snow;
+    for (uint32_t j = t; j < TXG_NLAT; j += TXG_TB) {
+      const txg_u64 n = Slat[j];
+      if (!n) continue;
+      const uint32_t ty = (j / LAT_RT_BINS) & 7u, r = j % LAT_RT_BINS;
+      if (j >= TXG_NLAT / 2) { atomicAdd((txg_u64 *)&lat->aborted_round_trips[ty][r], n); continue; }
+      atomicAdd((txg_u64 *)&lat->round_trips[ty][r], n);
+      atomicAdd((txg_u64 *)&lat->rt_sum[ty], n * r);
+      if (__hip_atomic_load(&lat->rt_max[ty], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < r) atomicMax((txg_u64 *)&lat->rt_max[ty], (txg_u64)r);
+      const uint64_t then = ring[(epoch - r) & (LAT_RING - 1)], dt = now > then ? now - then : 0;
+      atomicAdd((txg_u64 *)&lat->ticks[ty][lat_tick_bin(dt)], n);
+      atomicAdd((txg_u64 *)&lat->tick_sum[ty], n * dt);
+      if (__hip_atomic_load(&lat->tick_max[ty], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < dt) atomicMax((txg_u64 *)&lat->tick_max[ty], (txg_u64)dt);
+    }
+  }
 }
 
 template <class T>
@@ -277,6 +323,10 @@ struct dint_gdriver {
   uint8_t *d_batch[2][DINT_N_SHARDS] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
   uint32_t *d_counts = nullptr, *d_pub = nullptr, *d_ticket = nullptr, *d_zipf = nullptr;
   txg_stats *d_stats = nullptr;
+  bool lat = false;                      // DINT_DRIVER_LATENCY: launch the LAT instantiation of k_txn_emit
+  dint_driver_latency *d_lat = nullptr;  // ... which adds to these histograms
+  uint64_t *d_ring = nullptr;            // ... and stamps slot epoch & (LAT_RING - 1) of this ring
+  uint64_t tick_khz = 0;
   TxParams P{};
   uint32_t dbg = 0;  // DINT_TXN_DBG experiments: 1 = no look-back, 2 = no client logic
 };
@@ -313,15 +363,18 @@ template <class T>
 void launch_emit(dint_gdriver *g, hipStream_t st, bool fused) {
   const uint32_t b = g->cur, o = b ^ 1u;  // requests go into set b; the replies of the previous epoch sit in set o
 #define TXG_LAUNCH(W)                                                                                                      \
-  hipLaunchKernelGGL((k_txn_emit<T, W>), dim3(g->ntiles), dim3(TXG_TB), 0, st, (uint32_t *)g->d_clients,                     \
+  if (g->lat) TXG_LAUNCH_(W, true); else TXG_LAUNCH_(W, false)
+#define TXG_LAUNCH_(W, LAT)                                                                                                \
+  hipLaunchKernelGGL((k_txn_emit<T, W, LAT>), dim3(g->ntiles), dim3(TXG_TB), 0, st, (uint32_t *)g->d_clients,                \
                      (uint8_t *)g->d_store, g->cfg.n_clients, g->P, g->d_batch[b][0], g->d_batch[b][1], g->d_batch[b][2],    \
                      fused ? g->d_batch[o][0] : nullptr, fused ? g->d_batch[o][1] : nullptr, fused ? g->d_batch[o][2] : nullptr, \
                      g->cap, g->d_pub + (size_t)b * g->ntiles * 4, g->d_ticket + b, g->d_pub + (size_t)o * g->ntiles * 4,     \
-                     g->d_ticket + o, g->d_counts, g->d_stats, g->dbg)
-  if (g->waves == 3) TXG_LAUNCH(3);
-  else if (g->waves == 5) TXG_LAUNCH(5);
-  else TXG_LAUNCH(4);
+                     g->d_ticket + o, g->d_counts, g->d_stats, g->dbg, g->d_lat, g->d_ring, g->epochs)
+  if (g->waves == 3) { TXG_LAUNCH(3); }
+  else if (g->waves == 5) { TXG_LAUNCH(5); }
+  else { TXG_LAUNCH(4); }
 #undef TXG_LAUNCH
+#undef TXG_LAUNCH_
 }
 }  // namespace
 
@@ -331,6 +384,7 @@ int dint_gdriver_create(const dint_driver_config *cfg, int32_t device, uint32_t 
   if (!cfg || !out || cfg->n_clients == 0 || cfg->n_rows == 0 || cap_per_shard < 2) return DINT_EINVAL;
   if (cfg->workload != DINT_WL_TATP && cfg->workload != DINT_WL_SMALLBANK) return DINT_EINVAL;
   if (cfg->key_dist > 1 || (cfg->key_dist == 1 && !(cfg->zipf_theta > 0 && cfg->zipf_theta < 1))) return DINT_EINVAL;
+  if (cfg->flags & ~DINT_DRIVER_LATENCY) return DINT_EINVAL;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return DINT_ENODEV;
   if (device < 0 && hipGetDevice(&device) != hipSuccess) return DINT_ENODEV;
@@ -342,6 +396,7 @@ int dint_gdriver_create(const dint_driver_config *cfg, int32_t device, uint32_t 
   g->cap = cap_per_shard;
   g->msg = cfg->workload == DINT_WL_TATP ? 55 : 23;
   g->ntiles = (cfg->n_clients + TXG_TB - 1) / TXG_TB;
+  g->lat = (cfg->flags & DINT_DRIVER_LATENCY) != 0;
   if (getenv("DINT_TXN_DBG")) g->dbg = (uint32_t)atoi(getenv("DINT_TXN_DBG"));
   if (getenv("DINT_TXN_FUSE")) g->fuse = atoi(getenv("DINT_TXN_FUSE")) != 0;
   if (getenv("DINT_TXN_WAVES")) g->waves = atoi(getenv("DINT_TXN_WAVES"));
@@ -370,6 +425,16 @@ int dint_gdriver_create(const dint_driver_config *cfg, int32_t device, uint32_t 
               hipMemset(g->d_pub, 0, (size_t)g->ntiles * 32) != hipSuccess ||
               hipMemset(g->d_stats, 0, sizeof(txg_stats)) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
     rc = DINT_EHIP;
+  if (!rc && g->lat) {
+    int khz = 0;  // the rate of the clock the stamps are taken from; where the runtime has none to report: 100 MHz, ASSUMED
+    g->tick_khz = (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) ? (uint64_t)khz : 100000u;
+    (void)hipGetLastError();
+    if (hipMalloc((void **)&g->d_lat, sizeof(dint_driver_latency)) != hipSuccess || hipMalloc((void **)&g->d_ring, LAT_RING * 8) != hipSuccess)
+      rc = DINT_ENOMEM;
+    else if (hipMemset(g->d_lat, 0, sizeof(dint_driver_latency)) != hipSuccess || hipMemset(g->d_ring, 0, LAT_RING * 8) != hipSuccess ||
+             hipDeviceSynchronize() != hipSuccess)
+      rc = DINT_EHIP;
+  }
   if (rc) {
     dint_gdriver_destroy(g);
     return rc;
@@ -388,6 +453,7 @@ void dint_gdriver_destroy(dint_gdriver_t *g) {
     for (auto p : b) hipFree(p);
   if (g->ev_pending) hipEventDestroy(g->ev_pending);
   hipFree(g->d_counts); hipFree(g->d_pub); hipFree(g->d_ticket); hipFree(g->d_zipf); hipFree(g->d_stats);
+  hipFree(g->d_lat); hipFree(g->d_ring);
   delete g;
 }
 
@@ -460,6 +526,33 @@ int dint_gdriver_get_stats(dint_gdriver_t *g, dint_driver_stats *out, uint64_t *
   out->txns = s.txns; out->committed = s.committed; out->messages = s.messages; out->epochs = g->epochs;
   for (int k = 0; k < 8; k++) { out->by_type[k] = s.by_type[k]; out->committed_by_type[k] = s.committed_by_type[k]; }
   if (overflow) *overflow = s.overflow;
+  return 0;
+}
+
+int dint_gdriver_get_latency(dint_gdriver_t *g, dint_driver_latency *out) {
+  if (!g || !out) return DINT_EINVAL;
+  if (!g->lat) return DINT_ESTATE;
+  if (hipSetDevice(g->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return DINT_EHIP;
+  if (hipMemcpy(out, g->d_lat, sizeof *out, hipMemcpyDeviceToHost) != hipSuccess) return DINT_EHIP;
+  out->tick_khz = g->tick_khz;
+  out->epochs = g->epochs;
+  return 0;
+}
+
+// the histograms only: the ring and the clients' round-trip bytes go on, so a transaction under way keeps its whole latency
+int dint_gdriver_latency_reset(dint_gdriver_t *g, void *stream) {
+  if (!g) return DINT_EINVAL;
+  if (!g->lat) return DINT_ESTATE;
+  if (hipSetDevice(g->device) != hipSuccess) return DINT_EHIP;
+  return hipMemsetAsync(g->d_lat, 0, sizeof(dint_driver_latency), (hipStream_t)stream) == hipSuccess ? 0 : DINT_EHIP;
+}
+
+int dint_gdriver_read_stamps(dint_gdriver_t *g, uint64_t out[256], uint64_t *epochs) {
+  if (!g || !out) return DINT_EINVAL;
+  if (!g->lat) return DINT_ESTATE;
+  if (hipSetDevice(g->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return DINT_EHIP;
+  if (hipMemcpy(out, g->d_ring, LAT_RING * 8, hipMemcpyDeviceToHost) != hipSuccess) return DINT_EHIP;
+  if (epochs) *epochs = g->epochs;
   return 0;
 }
 

@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "txn_latency.h"
 #include "zipf_table.h"
 
 #if defined(__HIPCC__)
@@ -88,9 +89,10 @@ struct TxOut {
   uint8_t n;
   uint8_t shard[CAP], dst[CAP], src[CAP], type[CAP], ord[CAP];
   uint8_t n_fin, fin_txn[2], fin_ok[2];
-  uint16_t fresh;                // bit k: message k is a new request, built from table[k] / key[k]
+  uint8_t fin_rt[2];             // round trips of the finished transaction (txn_latency.h)
   uint8_t table[CAP];
-  uint64_t key[CAP];
+  uint16_t fresh;                // bit k: message k is a new request, built from table[k] / key[k]
+  uint64_t key[CAP];             // (fin_rt sits where the struct had padding: the queue's size in LDS is what it was)
   TX_HD void clear() { n = 0; n_fin = 0; fresh = 0; }
   // queue client message `src_msg` (sent with type `ty`) for shard s; its reply lands in client message `d`
   TX_HD void send(uint32_t s, uint8_t src_msg, uint8_t ty, uint8_t d) {
@@ -126,8 +128,8 @@ struct TxOut {
     m.ord = ord[k];
     return m;
   }
-  TX_HD void finish(uint8_t txn, bool committed) {
-    if (n_fin < 2) { fin_txn[n_fin] = txn; fin_ok[n_fin] = committed; }
+  TX_HD void finish(uint8_t txn, bool committed, uint8_t rt) {
+    if (n_fin < 2) { fin_txn[n_fin] = txn; fin_ok[n_fin] = committed; fin_rt[n_fin] = rt; }
     n_fin++;
   }
 };
@@ -172,7 +174,7 @@ struct TatpClient {
   uint32_t out_pos[6];
   TxMsgs<TatpMsg> m;  // [TATP_NMSG] -- set by the driver before every use (host vector / device array)
   uint8_t rt[TATP_NMSG], rv0[TATP_NMSG];  // per working message: type / val[0] of the last reply (or what the logic set)
-  uint8_t pad_[2];
+  uint8_t pad_[2];                        // pad_[0]: round trips of the running transaction (txn_latency.h)
   uint32_t rver[TATP_NMSG - 1];           // ... its version (TMP2 never needs one)
   uint32_t vlr;                           // UpdateLocation: the new vlr_location, parked until the subscriber row is read
   // a consumed reply: the three fields the logic may ask for.  (Unrolled over the message numbers, so that the arrays
@@ -230,6 +232,7 @@ TX_HD static inline uint64_t tatp_row_key(const TatpClient &c, uint8_t i) {
 }
 
 typedef TxOut<TatpMsg, 6> TatpOut;  // a tatp phase emits at most 6 messages
+static_assert(sizeof(TatpOut) == 96, "the phase queue of a tatp client");
 // a new request {type, table, key} to the key's primary; the reply's summary goes to working message i (TX_NO_DST:
 // nowhere), the whole reply too when the transaction will write the row back (full)
 TX_HD static inline void tatp_send_new(TatpOut &o, uint8_t i, uint8_t type, uint8_t table, uint64_t key, bool full = false) {
@@ -250,7 +253,7 @@ TX_HD static inline void tatp_send_bck(TatpClient &c, TatpOut &o, uint8_t ty, ui
   for (int i = 0; i < n; i++) o.send((uint32_t)((tatp_row_key(c, rows[i]) % 3 + 2) % 3), rows[i], ty, TX_NO_DST);
 }
 TX_HD static inline void tatp_finish(TatpClient &c, TatpOut &o, bool committed) {
-  o.finish(c.txn, committed);
+  o.finish(c.txn, committed, c.pad_[0]);
   c.step = 0;
 }
 
@@ -451,13 +454,15 @@ TX_HD static inline void tatp_emit(TatpClient &c, TatpOut &o) {
 // one phase of one client: emit messages (o.n > 0) -- finishing / starting transactions on the way
 TX_HD static inline void tatp_run(TatpClient &c, const TxParams &P, TatpOut &o) {
   o.clear();
+  bool began = false;  // a transaction began in this phase: its round trips start again (txn_latency.h)
   for (;;) {
-    if (c.step == 0) tatp_begin(c, P);
+    if (c.step == 0) { tatp_begin(c, P); began = true; }
     tatp_emit(c, o);
     if (o.n) break;  // waiting for replies
     // the phase emitted nothing: the transaction finished inside emit() -> start the next one
   }
   c.n_out = o.n;
+  tx_rt_count(c.pad_[0], began);
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
@@ -479,7 +484,7 @@ struct SbClient {
   uint8_t n_write, wr[3];  // indices into m[] of the rows written back
   uint8_t rel;        // abort: next row to release
   uint8_t out_shard[TX_MAXOUT], out_dst[TX_MAXOUT];
-  uint8_t pad0;
+  uint8_t pad0;       // round trips of the running transaction (txn_latency.h)
   float amount;
   uint64_t a0, a1;
   uint32_t out_pos[TX_MAXOUT];
@@ -490,6 +495,7 @@ struct SbClient {
 };
 static_assert(sizeof(SbClient) == 112, "client header");
 typedef TxOut<SbMsg, TX_MAXOUT> SbOut;
+static_assert(sizeof(SbOut) == 136, "the phase queue of a smallbank client");
 
 TX_HD static inline void sb_workgen(uint8_t *workgen) {
   // CreateWorkgenArr, smallbank/caladan/client_udp_shard.cc: same construction as tatp, mix smallbank.h:63-68
@@ -631,7 +637,7 @@ TX_HD static inline void sb_emit(SbClient &c, SbOut &o) {
           o.send((uint32_t)(c.m[i].key % 3), i, (c.m[i].type == S_GRANT_SH) ? S_REL_SH : S_REL_EX, TX_NO_DST);
         c.step = 7;
         return;
-      case 7: o.finish(c.txn, true); c.step = 0; return;
+      case 7: o.finish(c.txn, true, c.pad0); c.step = 0; return;
       case 20:  // abort: release the granted locks one round trip at a time (:248-279)
         while (c.rel < c.n_rows && !sb_granted(c.m[c.rel])) c.rel++;
         if (c.rel < c.n_rows) {
@@ -639,22 +645,24 @@ TX_HD static inline void sb_emit(SbClient &c, SbOut &o) {
           c.rel++;
           return;
         }
-        o.finish(c.txn, false);
+        o.finish(c.txn, false, c.pad0);
         c.step = 0;
         return;
-      default: o.finish(c.txn, false); c.step = 0; return;
+      default: o.finish(c.txn, false, c.pad0); c.step = 0; return;
     }
   }
 }
 
 TX_HD static inline void sb_run(SbClient &c, const TxParams &P, SbOut &o) {
   o.clear();
+  bool began = false;
   for (;;) {
-    if (c.step == 0) sb_begin(c, P);
+    if (c.step == 0) { sb_begin(c, P); began = true; }
     sb_emit(c, o);
     if (o.n) break;
   }
   c.n_out = o.n;
+  tx_rt_count(c.pad0, began);
   for (uint8_t k = 0; k < o.n; k++) { c.out_shard[k] = o.shard[k]; c.out_dst[k] = o.dst[k]; }
 }
 

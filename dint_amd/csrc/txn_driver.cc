@@ -13,10 +13,12 @@
 #include "../../include/dint_abi.h"
 #include "../../include/dint_driver.h"
 #include "txn_clients.h"
+#include "txn_latency.h"
 
 struct dint_driver {
   dint_driver_config cfg{};
   dint_driver_stats st{};
+  dint_driver_latency lat{};  // round-trip fields only (txn_latency.h)
   bool awaiting = false;
   virtual ~dint_driver() {}
   virtual int msg_size() const = 0;
@@ -86,6 +88,7 @@ struct HostDriver final : dint_driver {
       for (uint8_t k = 0; k < o.n_fin && k < 2; k++) {
         st.txns++; st.by_type[o.fin_txn[k]]++;
         if (o.fin_ok[k]) { st.committed++; st.committed_by_type[o.fin_txn[k]]++; }
+        lat_add_round_trips(&lat, o.fin_txn[k], o.fin_ok[k], o.fin_rt[k]);
       }
     }
     for (uint32_t s = 0; s < DINT_N_SHARDS; s++) counts[s] = (uint32_t)b[s].size();
@@ -103,6 +106,7 @@ extern "C" {
 
 int dint_driver_create(const dint_driver_config *cfg, dint_driver_t **out) {
   if (!cfg || !out || cfg->n_clients == 0 || cfg->n_rows == 0) return DINT_EINVAL;
+  if (cfg->flags & ~DINT_DRIVER_LATENCY) return DINT_EINVAL;
   if (cfg->key_dist > 1 || (cfg->key_dist == 1 && !(cfg->zipf_theta > 0 && cfg->zipf_theta < 1))) return DINT_EINVAL;
   try {
     if (cfg->workload == DINT_WL_TATP) *out = new HostDriver<TatpTraits>(*cfg);
@@ -135,4 +139,12 @@ int dint_driver_get_stats(const dint_driver_t *d, dint_driver_stats *out) {
   *out = d->st;
   return 0;
 }
+int dint_driver_get_latency(const dint_driver_t *d, dint_driver_latency *out) {
+  if (!d || !out) return DINT_EINVAL;
+  *out = d->lat;
+  out->epochs = d->st.epochs;
+  return 0;
+}
+uint32_t dint_latency_tick_bin_host(uint64_t ticks) { return lat_tick_bin(ticks); }
+uint64_t dint_latency_tick_lo_host(uint32_t bin) { return lat_tick_bin_lo(bin); }
 }

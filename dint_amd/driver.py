@@ -21,12 +21,87 @@ N_SHARDS = 3
 class DriverConfig(C.Structure):
     _fields_ = [("workload", C.c_uint32), ("n_clients", C.c_uint32), ("n_rows", C.c_uint64),
                 ("first_client", C.c_uint32), ("key_dist", C.c_uint32), ("zipf_theta", C.c_double),
-                ("reserved", C.c_uint32 * 8)]
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+#: dint_driver_config.flags (include/dint_driver.h)
+DRIVER_LATENCY = 1
+#: histogram sizes of dint_driver_latency
+LAT_RT_BINS, LAT_TICK_BINS = 32, 240
 
 
 class DriverStats(C.Structure):
     _fields_ = [("txns", C.c_uint64), ("committed", C.c_uint64), ("messages", C.c_uint64),
                 ("by_type", C.c_uint64 * 8), ("committed_by_type", C.c_uint64 * 8), ("epochs", C.c_uint64)]
+
+
+class DriverLatency(C.Structure):
+    """dint_driver_latency (include/dint_driver.h)"""
+    _fields_ = [("round_trips", (C.c_uint64 * LAT_RT_BINS) * 8), ("aborted_round_trips", (C.c_uint64 * LAT_RT_BINS) * 8),
+                ("rt_sum", C.c_uint64 * 8), ("rt_max", C.c_uint64 * 8), ("ticks", (C.c_uint64 * LAT_TICK_BINS) * 8),
+                ("tick_sum", C.c_uint64 * 8), ("tick_max", C.c_uint64 * 8), ("tick_khz", C.c_uint64), ("epochs", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        """histograms as uint64 arrays [type, bin], sums and maxima as [type]"""
+        d = {k: np.array(getattr(self, k), dtype=np.uint64) for k in
+             ("round_trips", "aborted_round_trips", "rt_sum", "rt_max", "ticks", "tick_sum", "tick_max")}
+        d["tick_khz"], d["epochs"] = int(self.tick_khz), int(self.epochs)
+        return d
+
+
+def tick_bin(ticks: int) -> int:
+    """the tick histogram's bin of a value (csrc/txn_latency.h lat_tick_bin)"""
+    return int(_bind().dint_latency_tick_bin_host(ticks))
+
+
+def tick_bin_lo(b: int) -> int:
+    """the smallest value of a tick bin (LAT_TICK_BINS: where the last bin would end if it did not saturate)"""
+    return int(_bind().dint_latency_tick_lo_host(b))
+
+
+def merge_latency(lats) -> dict:
+    """the latency of several client groups as one (:meth:`Driver.latency` / :meth:`GpuDriver.latency` dicts): histograms and
+    sums add, maxima take the maximum; tick_khz is the groups' common rate (0 from host drivers), epochs the largest count"""
+    lats = list(lats)
+    khz = {l["tick_khz"] for l in lats if l["tick_khz"]}
+    if len(khz) > 1:
+        raise ValueError(f"the groups' clocks differ: {sorted(khz)} kHz")
+    out = {k: np.sum([l[k] for l in lats], axis=0, dtype=np.uint64) for k in ("round_trips", "aborted_round_trips", "rt_sum", "ticks", "tick_sum")}
+    for k in ("rt_max", "tick_max"):
+        out[k] = np.max([l[k] for l in lats], axis=0).astype(np.uint64)
+    out["tick_khz"], out["epochs"] = (khz.pop() if khz else 0), max(l["epochs"] for l in lats)
+    return out
+
+
+def latency_percentiles(lat: dict, kind: str = "ticks", ps=(50, 99, 99.9), types=None) -> dict:
+    """Average and percentiles of COMMITTED transactions from a latency dict, by the reference's rule (Percentile(),
+    tatp/caladan/stat.h:12-17): the element at index floor(p * n / 100) of the sorted samples -- in a histogram the first bin
+    whose cumulative count exceeds that index (the last sample for an index of n: p = 100).  kind = "round_trips": values
+    in round trips (the last bin stands for 31 and more).  kind = "ticks": a bin is reported by its lower bound, converted
+    to microseconds with tick_khz; the average comes from the exact tick sum.  `types` = the transaction types to pool
+    (default: all).  Returns {"n", "avg", "max", "p": {p: value}}; with n = 0 every value is None."""
+    if kind not in ("ticks", "round_trips"):
+        raise ValueError(kind)
+    if kind == "ticks" and not lat["tick_khz"]:
+        raise ValueError("no tick rate: ticks are kept by the GPU-resident driver only")
+    ts = list(range(8)) if types is None else list(types)
+    hist = np.asarray(lat[kind], dtype=np.uint64)[ts].sum(axis=0, dtype=np.uint64)
+    n = int(hist.sum())
+    if n == 0:
+        return {"n": 0, "avg": None, "max": None, "p": {p: None for p in ps}}
+    if kind == "ticks":
+        unit = 1000.0 / lat["tick_khz"]  # microseconds per tick
+        value = lambda b: tick_bin_lo(b) * unit  # noqa: E731
+        total, top = int(np.asarray(lat["tick_sum"])[ts].sum(dtype=np.uint64)) * unit, int(np.asarray(lat["tick_max"])[ts].max()) * unit
+    else:
+        value = lambda b: b  # noqa: E731
+        total, top = int(np.asarray(lat["rt_sum"])[ts].sum(dtype=np.uint64)), int(np.asarray(lat["rt_max"])[ts].max())
+    cum = np.cumsum(hist, dtype=np.uint64)
+    out = {}
+    for p in ps:
+        idx = min(int(float(p) * n / 100), n - 1)  # in double arithmetic, as the reference computes it
+        out[p] = value(int(np.searchsorted(cum, idx, side="right")))
+    return {"n": n, "avg": total / n, "max": top, "p": out}
 
 
 def _bind():
@@ -41,6 +116,9 @@ def _bind():
     L.dint_driver_batch.restype, L.dint_driver_batch.argtypes = vp, [vp, u32]
     L.dint_driver_consume.restype, L.dint_driver_consume.argtypes = C.c_int, [vp, C.POINTER(vp * N_SHARDS)]
     L.dint_driver_get_stats.restype, L.dint_driver_get_stats.argtypes = C.c_int, [vp, C.POINTER(DriverStats)]
+    L.dint_driver_get_latency.restype, L.dint_driver_get_latency.argtypes = C.c_int, [vp, C.POINTER(DriverLatency)]
+    L.dint_latency_tick_bin_host.restype, L.dint_latency_tick_bin_host.argtypes = u32, [C.c_uint64]
+    L.dint_latency_tick_lo_host.restype, L.dint_latency_tick_lo_host.argtypes = C.c_uint64, [u32]
     L._driver_bound = True
     return L
 
@@ -95,17 +173,24 @@ class Driver:
         return {"txns": s.txns, "committed": s.committed, "messages": s.messages, "epochs": s.epochs,
                 "by_type": list(s.by_type), "committed_by_type": list(s.committed_by_type)}
 
+    def latency(self) -> dict:
+        """round trips of the finished transactions per type (DriverLatency.as_dict; the tick fields are 0 on the host)"""
+        l = DriverLatency()
+        _lib.check(self._L.dint_driver_get_latency(self._h, C.byref(l)))
+        return l.as_dict()
+
 
 class GpuDriver:
     """The same closed-loop clients resident on the GPU (csrc/k_txn.hip, include/dint_driver.h dint_gdriver_*):
     ``next(stream)`` emits the epoch's three request batches into device arrays (``batch_ptr[s]``, refreshed by every
     ``next``; live sizes at ``counts_ptr``), the shard servers answer in place, ``consume(stream)`` feeds the replies
     back (on the stream of ``next``: fused into the next emit kernel).  The request stream is bit-identical to
-    :class:`Driver`'s."""
+    :class:`Driver`'s.  ``latency=True`` (DINT_DRIVER_LATENCY) keeps the committed transactions' latency in round trips
+    and in ticks of the device clock: ``latency()``, ``latency_reset(stream)``; the request stream is the same bytes."""
 
     def __init__(self, workload: Workload, n_clients: int, n_rows: int, cap: int, *, first_client: int = 0,
-                 zipf_theta: float | None = None, device: int = -1):
-        L = self._L = _lib.load()
+                 zipf_theta: float | None = None, device: int = -1, latency: bool = False, flags: int = 0):
+        L = self._L = _bind()
         vp, u32 = C.c_void_p, C.c_uint32
         L.dint_gdriver_create.restype, L.dint_gdriver_create.argtypes = C.c_int, [C.POINTER(DriverConfig), C.c_int32, u32, C.POINTER(vp)]
         L.dint_gdriver_destroy.restype, L.dint_gdriver_destroy.argtypes = None, [vp]
@@ -115,11 +200,15 @@ class GpuDriver:
         L.dint_gdriver_counts.restype, L.dint_gdriver_counts.argtypes = vp, [vp]
         L.dint_gdriver_get_stats.restype, L.dint_gdriver_get_stats.argtypes = C.c_int, [vp, C.POINTER(DriverStats), C.POINTER(C.c_uint64)]
         L.dint_gdriver_read_batch.restype, L.dint_gdriver_read_batch.argtypes = C.c_int64, [vp, u32, vp, C.c_uint64]
+        L.dint_gdriver_get_latency.restype, L.dint_gdriver_get_latency.argtypes = C.c_int, [vp, C.POINTER(DriverLatency)]
+        L.dint_gdriver_latency_reset.restype, L.dint_gdriver_latency_reset.argtypes = C.c_int, [vp, vp]
+        L.dint_gdriver_read_stamps.restype, L.dint_gdriver_read_stamps.argtypes = C.c_int, [vp, C.POINTER(C.c_uint64 * 256), C.POINTER(C.c_uint64)]
         self.workload = Workload(workload)
         self.dtype = MSG_DTYPE[self.workload]
         self.cap = cap
         cfg = DriverConfig(workload=int(workload), n_clients=n_clients, n_rows=n_rows, first_client=first_client,
-                           key_dist=0 if zipf_theta is None else 1, zipf_theta=zipf_theta or 0.0)
+                           key_dist=0 if zipf_theta is None else 1, zipf_theta=zipf_theta or 0.0,
+                           flags=flags | (DRIVER_LATENCY if latency else 0))
         h = vp()
         rc = L.dint_gdriver_create(C.byref(cfg), device, cap, C.byref(h))
         if rc:
@@ -157,6 +246,29 @@ class GpuDriver:
             raise _lib.DintError(f"dint_gdriver_get_stats failed: {rc}")
         return {"txns": s.txns, "committed": s.committed, "messages": s.messages, "epochs": s.epochs,
                 "by_type": list(s.by_type), "committed_by_type": list(s.committed_by_type), "overflow": ov.value}
+
+    def latency(self) -> dict:
+        """latency of the finished transactions (DriverLatency.as_dict); synchronises.  Needs latency=True."""
+        l = DriverLatency()
+        rc = self._L.dint_gdriver_get_latency(self._h, C.byref(l))
+        if rc:
+            raise _lib.DintError(f"dint_gdriver_get_latency failed: {rc}")
+        return l.as_dict()
+
+    def latency_reset(self, stream: int = 0):
+        """zero the histograms in stream order (the reference's stat_started window); transactions under way keep their latency"""
+        rc = self._L.dint_gdriver_latency_reset(self._h, stream)
+        if rc:
+            raise _lib.DintError(f"dint_gdriver_latency_reset failed: {rc}")
+
+    def read_stamps(self):
+        """(uint64[256] epoch stamps: slot e & 255 = the clock at the start of epoch e's emit kernel, epochs emitted);
+        synchronises (tests and debugging)"""
+        out, ep = (C.c_uint64 * 256)(), C.c_uint64()
+        rc = self._L.dint_gdriver_read_stamps(self._h, C.byref(out), C.byref(ep))
+        if rc:
+            raise _lib.DintError(f"dint_gdriver_read_stamps failed: {rc}")
+        return np.array(out, dtype=np.uint64), ep.value
 
     def read_batches(self):
         """host copies of the current epoch's three batches (synchronises; tests and debugging)"""

@@ -41,8 +41,14 @@ typedef struct dint_driver_config {
    * picker, smallbank.h:30-50); 1 = Zipf(theta) over the rows (BASELINE.json's stress distribution) */
   uint32_t key_dist;
   double zipf_theta;
-  uint32_t reserved[8];
+  uint32_t flags;         /* DINT_DRIVER_*; a bit no flag names: DINT_EINVAL from both *_create calls (was reserved[0]) */
+  uint32_t reserved[7];
 } dint_driver_config;
+
+/* dint_driver_config.flags.  DINT_DRIVER_LATENCY: the GPU-resident driver keeps the latency histograms below (its emit kernel is
+ * then another instantiation, with 2 KB more LDS and a few device atomics per workgroup and epoch); the host driver always keeps
+ * its round-trip fields and ignores the flag.  The request stream is the same bytes with and without it. */
+#define DINT_DRIVER_LATENCY 1u
 
 typedef struct dint_driver_stats {
   uint64_t txns;          /* finished transactions (committed or not) = the reference's "throughput" count */
@@ -66,6 +72,41 @@ const void *dint_driver_batch(dint_driver_t *d, uint32_t shard);
 int dint_driver_consume(dint_driver_t *d, const void *const replies[DINT_N_SHARDS]);
 int dint_driver_get_stats(const dint_driver_t *d, dint_driver_stats *out);
 
+/* ---- transaction latency (dint_amd/csrc/txn_latency.h) ---------------------------------------------------------
+ * The reference clients print average, median, 99th and 99.9th percentile latency of COMMITTED transactions beside
+ * throughput and goodput (tatp/caladan/client_udp_shard.cc:94-107, :1148-1182; one sample per committed transaction,
+ * Percentile() of tatp/caladan/stat.h:12-17).  This is a different quantity from the EPOCH latency of the servers' passes
+ * that bench.py reports.  Two measures, per transaction type (the first index: the type numbers of by_type[]):
+ *   round trips  r = the epochs in which the transaction emitted messages: it began inside the emit of epoch b, was
+ *                finished inside the emit of epoch f, r = f - b.  Histogram index min(r, DINT_LAT_RT_BINS - 1); rt_sum and
+ *                rt_max hold r itself (at most 255: the count saturates there).  Both drivers.
+ *   ticks        of the device's constant-rate clock, GPU-resident driver only: from the start of the emit kernel of
+ *                epoch b to the moment the workgroup that finished the transaction read its clock in epoch f (once per
+ *                workgroup, after its clients' phases and their messages).  Log-linear histogram: values below 16 map to
+ *                themselves, above that 8 bins per power of two (a bin is at most 12.5 % wide), the last bin saturates at
+ *                1.875 * 2^31 ticks (40 s at 100 MHz); dint_latency_tick_lo_host(bin) = the smallest value of a bin.
+ *                tick_sum / tick_max hold exact ticks.  A transaction that took more than 31 round trips is timed from
+ *                epoch f - 31.
+ * aborted_round_trips counts the transactions that did not commit.  That is an extension: the reference samples
+ * committed transactions only, and every other field here does the same. */
+#define DINT_LAT_RT_BINS 32
+#define DINT_LAT_TICK_BINS 240
+typedef struct dint_driver_latency {
+  uint64_t round_trips[8][DINT_LAT_RT_BINS];         /* committed transactions */
+  uint64_t aborted_round_trips[8][DINT_LAT_RT_BINS]; /* the others (extension) */
+  uint64_t rt_sum[8], rt_max[8];                     /* committed */
+  uint64_t ticks[8][DINT_LAT_TICK_BINS];             /* committed; GPU-resident driver, else 0 */
+  uint64_t tick_sum[8], tick_max[8];
+  uint64_t tick_khz; /* ticks per millisecond: hipDeviceAttributeWallClockRate.  Where the runtime does not report one, 100000
+                      * (the 100 MHz of the CDNA parts' constant clock): ASSUMED then, not read.  0 from the host driver. */
+  uint64_t epochs;   /* epochs emitted so far (not reset) */
+} dint_driver_latency;
+/* round-trip fields and epochs; the tick fields and tick_khz are 0.  Always kept: the host driver has no hot path to protect */
+int dint_driver_get_latency(const dint_driver_t *d, dint_driver_latency *out);
+/* the tick bin rule on the host, for tests and tools (no device call) */
+uint32_t dint_latency_tick_bin_host(uint64_t ticks);
+uint64_t dint_latency_tick_lo_host(uint32_t bin); /* bin = DINT_LAT_TICK_BINS: 2^32, where the last bin would end */
+
 /* ---- the same drivers, resident on the GPU -----------------------------------------------
  * Client state lives in HBM; dint_gdriver_next launches a kernel in which every client runs one phase and emits its
  * messages into three driver-owned device arrays -- at exactly the positions, hence with exactly the bytes, of the
@@ -88,6 +129,16 @@ uint32_t dint_gdriver_cap(const dint_gdriver_t *g);
 /* tests / debugging: synchronise and copy the current batch of `shard` to the host; returns its message count */
 int64_t dint_gdriver_read_batch(dint_gdriver_t *g, uint32_t shard, void *host, uint64_t cap_msgs);
 int dint_gdriver_get_stats(dint_gdriver_t *g, dint_driver_stats *out, uint64_t *overflow);  /* synchronises the device */
+/* Transaction latency (struct dint_driver_latency above) of a driver created with DINT_DRIVER_LATENCY; without the flag both
+ * calls return DINT_ESTATE.  dint_gdriver_get_latency synchronises the device, like dint_gdriver_get_stats.
+ * dint_gdriver_latency_reset zeroes the histograms, sums and maxima in stream order -- the reference's `stat_started` window:
+ * issue it on the loop's stream after the warm-up epochs.  The epoch stamps and the clients' round-trip counts are not touched,
+ * so a transaction that began before the reset and commits after it is counted with its whole latency. */
+int dint_gdriver_get_latency(dint_gdriver_t *g, dint_driver_latency *out);
+int dint_gdriver_latency_reset(dint_gdriver_t *g, void *stream);
+/* tests / debugging: synchronise and copy the 256 epoch stamps (slot e & 255 = the clock at the start of the emit kernel of epoch
+ * e, 0 where no epoch wrote yet) and the number of epochs emitted.  DINT_ESTATE without DINT_DRIVER_LATENCY. */
+int dint_gdriver_read_stamps(dint_gdriver_t *g, uint64_t out[256], uint64_t *epochs);
 
 /* ---- lock_fasst load generator ---------------------------------------------------------------------------
  * lock_fasst/caladan/client.cc:183-280 (ClientLoop) over transactions shaped like lock_fasst/caladan/trace_init.sh
